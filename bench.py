@@ -13,7 +13,12 @@ only that frame's 8 views, so the step has no collective; the one real exchange,
 the all-gather of every rank's per-view 2D keypoints that feeds the clip-level
 Viterbi / optim_points stage, runs once inside the timed region.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds every other
+leg after the headline (clip lift, sustained / multi-frame / overlapped-H2D steps, configs 4 and 5, the 3D
+parity check, the CPU baseline) as extra keys of the same line; --dump-outputs DIR writes the last timed
+step's outputs as DIR/<name>.npy (same arguments -> same inputs, so two builds compare output for output).
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
 """
 from __future__ import annotations
 
@@ -45,13 +50,25 @@ def parse():
     ap.add_argument("--frames-per-step", type=int, default=1)
     ap.add_argument("--model", default="huge", choices=["huge", "base", "tiny"])
     ap.add_argument("--resident-frames", type=int, default=4)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-lift", action="store_true", help="skip the config-4 lift timing (extra keys)")
-    ap.add_argument("--no-config5", action="store_true", help="skip the config-5 detector + pose timing (extra keys)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every other leg (extra keys): the clip lift, the sustained / "
+                         "multi-frame-batch / overlapped-H2D measurements, the config-4 and config-5 timings, the 3D "
+                         "parity check and the CPU baseline; the --no-* options below drop legs of a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (2D keypoints, scores, argmax, 3D points, heatmaps) "
+                         "as DIR/<name>.npy after the timed steps")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and 3D parity legs")
+    ap.add_argument("--no-lift", action="store_true", help="--full without the clip lift and config-4 lift timings")
+    ap.add_argument("--no-config5", action="store_true", help="--full without the config-5 detector + pose timing")
     ap.add_argument("--graph", action="store_true", help="replay the forward as a hipGraph (disables live timing)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the multi-frame-batch and overlapped-H2D measurements (extra keys)")
-    return ap.parse_args()
+                    help="--full without the sustained, multi-frame-batch and overlapped-H2D measurements; also keeps "
+                         "one resident frame set per frame slot instead of four")
+    args = ap.parse_args()
+    if not args.full:
+        # a plain run measures the headline only; the resident-frame count (--no-extras) is left as given
+        args.no_cpu_baseline = args.no_lift = args.no_config5 = True
+    return args
 
 
 def log(msg):
@@ -611,6 +628,32 @@ class Pipeline:
             log[:, :, 2] = self.score
 
 
+DUMP_LIMIT_BYTES = 60_000_000   # all files of one --dump-outputs together (every rank's)
+
+
+def dump_outputs(pipe, out_dir, rank=0, world=1):
+    """What the step last run on `pipe` returned to its caller, as <out_dir>/<name>.npy (ranks above 0:
+    <name>_rank<r>.npy): kp2d (n, J, 2) f64 image pixels, score (n, J) and argmax (n, J) as f32, kp3d (frames,
+    individuals x J, 3) f64 (NaN where too few views scored), heatmaps (n, J, 64, 48) f32.  The heatmaps
+    take what the other arrays leave of this rank's share of DUMP_LIMIT_BYTES: when larger (several frames per
+    step), a seeded sample of their flattened elements, the same elements in every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"kp2d": pipe.kp.cpu().numpy(), "score": pipe.score.float().cpu().numpy(),
+              "argmax": pipe.am.float().cpu().numpy(), "kp3d": pipe.p3d.cpu().numpy()}
+    left = DUMP_LIMIT_BYTES // world - sum(a.nbytes for a in arrays.values()) - 4096   # 128 B of .npy header per file
+    hm = pipe.hm.float().cpu().numpy()
+    if hm.nbytes > left:
+        pick = np.sort(np.random.default_rng(0).choice(hm.size, size=left // hm.itemsize, replace=False))
+        hm = hm.reshape(-1)[pick]
+    arrays["heatmaps"] = hm
+    suffix = "" if rank == 0 else f"_rank{rank}"
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), np.ascontiguousarray(a))
+    log(f"outputs of the last timed step -> {out_dir}: " + ", ".join(f"{k}{v.shape}" for k, v in arrays.items()))
+
+
 def multi_frame_batches(model, cams_dev, boxes_all, frames, counts=(2, 4), steps=20, warmup=3):
     """BASELINE config 3's per-GPU batch choice: the same step with `fps` frames per launch sequence
     (M = fps x 64 x 192 GEMM rows), ms per step and individuals x frames / s per setting."""
@@ -730,14 +773,17 @@ def main():
     model = VitPoseHip(cfg, weights, device=local, graph=args.graph)
     del weights
     lib = model.lib
-    extras = rank == 0 and world == 1 and not args.no_extras
+    # the one-GPU run keeps four resident frame sets per frame slot (what the multi-frame batches of --full need), with
+    # or without --full, so the headline's inputs and its value do not depend on --full
+    wide = rank == 0 and world == 1 and not args.no_extras
+    extras = wide and args.full
 
     # ---------------- synthetic, HBM-resident inputs (this rank's frames)
     cams_np = synth.make_cameras(N_VIEWS)
     group = CameraGroup.from_dicts(cams_np, device=local)
     cams_dev = group.cams_tensor()
     FPS = args.frames_per_step
-    NF = args.resident_frames * max(FPS, 4 if extras else 1)          # resident frames (4 per frame slot)
+    NF = args.resident_frames * max(FPS, 4 if wide else 1)            # resident frames (4 per frame slot)
     skel = synth.make_skeletons(N_ANIMALS, NF, seed=2 + rank)
     kp2d = synth.make_kp2d(cams_np, skel, seed=3 + rank)            # (A, F, C, J, 3)
     boxes = []
@@ -850,6 +896,8 @@ def main():
         "gather_bytes_per_rank": int(args.steps * FPS * N_VIEWS * N_ANIMALS * cfg.n_joints * 3 * 4),
     }
     log(f"timed region {dt:.3f} s")
+    if args.dump_outputs:
+        dump_outputs(pipe, args.dump_outputs, rank, world)   # before any other leg runs a step on `pipe`
     if not args.no_lift:
         # BASELINE config 3's last stage: the clip lift of every frame the ranks just processed, its individuals
         # split over the ranks as in run_demo's sharded step 4; the slowest rank's time

@@ -30,7 +30,7 @@ def test_bench_two_ranks_sharing_the_gpu():
     steps = 3
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--steps", str(steps),
-           "--warmup", "1", "--no-cpu-baseline", "--no-extras", "--no-config5"]
+           "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extras", "--no-config5"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

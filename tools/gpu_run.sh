@@ -5,9 +5,11 @@
 # ends the run (no GPU step after a fault).  Steps:
 #   tests[:<pytest args>]  pytest -m gpu (all GPU tests, or the given files / -k expression)
 #   smoke                  __graft_entry__.smoke()
-#   bench[:<args>]         python bench.py <args>  (JSON line -> <out>/bench.json)
+#   bench[:<args>]         python bench.py <args>  (JSON line -> <out>/bench<i>.json; bench:--full for every leg)
 #   bench2[:<args>]        bench.py as 2 ranks sharing the one GPU over gloo (MQ_BENCH_SHARE_GPU=1): a rehearsal
 #                          of the multi-rank path (gather, max-over-ranks, the split clip lift)
+#   rccl1[:<args>]         bench.py as 1 rank with the RCCL process group forced (MQ_BENCH_DIST=1, NCCL_DEBUG=INFO):
+#                          the N > 1 code on one GPU; the log's RCCL version / init lines are printed
 #   prof[:<args>]          rocprofv3 --kernel-trace --stats over bench.py <args> -> <out>/prof/
 #   tool:<script> [args]   python tools/<script> <args>
 #   profpy:<script> [args] rocprofv3 --kernel-trace --stats over python tools/<script>
@@ -40,6 +42,10 @@ for step in "$@"; do
     bench2) run "bench2_$i" 900 env MQ_BENCH_SHARE_GPU=1 MQ_BENCH_BACKEND=gloo python -u -m torch.distributed.run --nnodes=1 \
               --nproc-per-node 2 --master-addr 127.0.0.1 --master-port $((29540 + i)) bench.py --gpus 2 $arg || exit $?
             grep '^{' "$out/bench2_$i.log" | tail -1 > "$out/bench2_$i.json" ;;
+    rccl1) run "rccl1_$i" 900 env MQ_BENCH_DIST=1 NCCL_DEBUG=INFO python -u -m torch.distributed.run --nnodes=1 \
+              --nproc-per-node 1 --master-addr 127.0.0.1 --master-port $((29560 + i)) bench.py --gpus 1 $arg || exit $?
+            grep '^{' "$out/rccl1_$i.log" | tail -1 > "$out/rccl1_$i.json"
+            grep -h -i "rccl version\|Init COMPLETE" "$out/rccl1_$i.log" | head -5 || true ;;
     prof) run "prof$i" 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/prof$i" -o run -- python3 -u bench.py $arg || exit $? ;;
     tool) run "tool$i" 900 python -u tools/$arg || exit $? ;;
     profpy) run "profpy$i" 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/profpy$i" -o run -- python3 -u tools/$arg || exit $? ;;
