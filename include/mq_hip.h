@@ -454,6 +454,62 @@ int mq_optim_points(mq_ctx* ctx, const double* cams, int n_cams, const double* p
                     double reproj_error_threshold, int reproj_loss, int n_deriv_smooth, int fix_lengths,
                     int max_iter, double ftol, int solver, double* stats, void* stream);
 
+/* ---- Camera-motion compensation for BoT-SORT (csrc/cmc.hip): boxmot 12.0.7 cmc/sift.py SIFT.apply restated
+ * stage by stage, HIP from the uint8 frame to the 2x3 warp.  tests/cmc_ref.py is the numpy restatement the
+ * kernels mirror; cv2 parity is unpinned.  All pointers are device pointers unless marked host. */
+typedef struct mq_cmc mq_cmc;
+
+/* cv2.cvtColor(BGR2GRAY) + cv2.resize(fx = fy = scale, INTER_LINEAR) in cv2's fixed-point arithmetic:
+ * frames uint8 (n_img, height, width, 3) -> gray_out uint8 (n_img, rint(height scale), rint(width scale)). */
+int mq_cmc_preprocess(mq_ctx* ctx, const uint8_t* frames, int64_t frame_stride, int n_img, int height, int width,
+                      double scale, uint8_t* gray_out, void* stream);
+
+/* cv2.SIFT_create(nOctaveLayers=3, contrastThreshold=0.02, edgeThreshold=20).detect (Lowe 2004; sigma 1.6,
+ * assumed input blur 0.5): first_octave -1 (2x upsampled base, cv2's default) or 0; mask uint8 (n_img, height,
+ * width) or null (a keypoint is dropped where mask[rint(y), rint(x)] == 0, cv2 runByPixelsMask).
+ * kps_out float32 (n_img, max_kp, 7) [x, y, size, angle, octave, layer, response] sorted by (octave, layer, y, x,
+ * angle), the first max_kp (<= 2048) of them; counts_out int32 (n_img).  dog_out (null, or float32 (n_img,
+ * sum over octaves of 5 h_o w_o)) receives the difference-of-Gaussian pyramid, octave-major. */
+int mq_sift_detect(mq_ctx* ctx, const uint8_t* gray, int n_img, int height, int width, int first_octave,
+                   const uint8_t* mask, int max_kp, float* kps_out, int32_t* counts_out, float* dog_out,
+                   void* stream);
+
+/* cv2 SIFT compute (calcSIFTDescriptor, 4 x 4 x 8, clip 0.2, x 512, saturate to uint8) for the first counts[i]
+ * keypoints of image i: desc_out uint8 (n_img, max_kp, 128). */
+int mq_sift_describe(mq_ctx* ctx, const uint8_t* gray, int n_img, int height, int width, int first_octave,
+                     const float* kps, const int32_t* counts, int max_kp, uint8_t* desc_out, void* stream);
+
+/* cv2.BFMatcher(NORM_L2).knnMatch(query, train, k = 2) on the integer squared distance: query / train uint8
+ * (n_img, max_kp, 128) with n_query / n_train int32 (n_img) rows in use; idx_out / dist_out int32 (n_img, max_kp,
+ * 2), -1 where absent; on equal distance the lower train index comes first. */
+int mq_desc_match_knn2(mq_ctx* ctx, const uint8_t* query, const int32_t* n_query, const uint8_t* train,
+                       const int32_t* n_train, int n_img, int max_kp, int32_t* idx_out, int32_t* dist_out,
+                       void* stream);
+
+/* cv2.estimateAffinePartial2D(src, dst, method = RANSAC, threshold) with a deterministic hypothesis set (every
+ * pair when there are <= 2000, else 2000 hashed pairs) and a closed-form least-squares refit over the inliers:
+ * pts float64 (n_sets, max_pts, 4) [src x, src y, dst x, dst y], counts int32 (n_sets); warps_out float64
+ * (n_sets, 6) row-major 2x3 (identity for <= 4 points), info_out int32 (n_sets, 2) [hypothesis, inliers],
+ * mask_out uint8 (n_sets, max_pts). */
+int mq_affine_partial_ransac(mq_ctx* ctx, const double* pts, const int32_t* counts, int n_sets, int max_pts,
+                             double threshold, double* warps_out, int32_t* info_out, uint8_t* mask_out, void* stream);
+
+/* boxmot SIFT(downscale = 1 / scale) for n_slots cameras: a slot holds one camera's previous keypoints and
+ * descriptors on the device.  max_kp <= 2048. */
+int mq_cmc_create(mq_ctx* ctx, int n_slots, int height, int width, double scale, int max_kp, mq_cmc** out);
+int mq_cmc_destroy(mq_cmc* cmc);
+/* forget the previous frame of a slot (-1: of every slot) */
+int mq_cmc_reset(mq_cmc* cmc, int slot);
+/* SIFT.apply for n_img frames at once (all cameras of a time step): frames uint8 BGR (n_img, height, width, 3);
+ * slots host int32 (n_img), distinct; boxes host float64 (n_img, max_boxes, 4) x1 y1 x2 y2 with box_counts host
+ * int32 (n_img) (max_boxes 0: none); warps_out host float64 (n_img, 6): previous-frame -> current-frame
+ * coordinates at full resolution, the identity on a slot's first frame or with <= 4 good matches; stats_out host
+ * int32 (n_img, 4) [keypoints, matches after ratio + gate, good matches, inliers] or null.  Synchronises the
+ * stream. */
+int mq_cmc_apply(mq_cmc* cmc, const uint8_t* frames, int64_t frame_stride, int n_img, const int32_t* slots,
+                 const double* boxes, const int32_t* box_counts, int max_boxes, double* warps_out, int32_t* stats_out,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,7 @@
 #include <string>
 #include <vector>
 
+#include "cmc.hpp"
 #include "geometry.hpp"
 #include "detector.hpp"
 #include "idcls.hpp"
@@ -81,6 +82,7 @@ struct mq_ctx {
   DevBuf assoc_ws;  // step-2 affinity: rays + pairwise distances
   DevBuf det_ws;    // detector post-processing (sort, NMS masks)
   DevBuf dlt_ws;    // mq_triangulate_dlt: undistorted points
+  mq::SiftWs* sift_ws = nullptr;  // SIFT pyramid + candidates of the stage entry points (mq_sift_*)
 };
 
 struct ParamSlot {
@@ -237,6 +239,7 @@ int mq_destroy(mq_ctx* ctx) {
   ctx->assoc_ws.release();
   ctx->dlt_ws.release();
   ctx->det_ws.release();
+  mq::sift_ws_destroy(ctx->sift_ws);
   delete ctx;
   return 0;
 }
@@ -1269,6 +1272,243 @@ int mq_attention_bf16(mq_ctx* ctx, const uint16_t* qkv, uint16_t* out, int n_img
   HIP_TRY(hipSetDevice(ctx->device));
   const int rc = mq::attention_bf16(qkv, out, n_img, tokens, dim, heads, (hipStream_t)stream);
   if (rc != 0) return fail("mq_attention_bf16: unsupported shape (tokens % 32 == 0, <= 192; head dim 64 or 80)", -2);
+  return 0;
+}
+
+}  // extern "C"
+
+// ----------------------------------------------------------------------------- camera-motion compensation
+struct mq_cmc {
+  mq_ctx* ctx;
+  int n_slots, H, W, h, w, max_kp;
+  double scale;
+  mq::SiftWs* ws = nullptr;
+  // per-slot previous frame
+  float* prev_kps = nullptr;
+  uint8_t* prev_desc = nullptr;
+  int32_t* prev_cnt = nullptr;
+  // per-call work, sized for cap images
+  DevBuf work;
+  int cap = 0, cap_boxes = 0;
+  uint8_t *gray, *mask, *desc, *inl;
+  float* kps;
+  int32_t *cnt, *idx, *dist, *n_knn, *n_good, *info, *slots, *box_cnt;
+  double *tmp, *good, *warps, *boxes;
+};
+
+namespace {
+
+size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+int cmc_reserve(mq_cmc* c, int n, int max_boxes) {
+  if (n <= c->cap && max_boxes <= c->cap_boxes) return 0;
+  n = std::max(n, c->cap);
+  max_boxes = std::max(max_boxes, c->cap_boxes);
+  const size_t N = (size_t)n, K = (size_t)c->max_kp, hw = (size_t)c->h * c->w;
+  const size_t sizes[17] = {N * hw,    N * hw,    N * K * 128, N * K,      N * K * 7 * 4, N * 4,
+                            N * K * 8, N * K * 8, N * 4,       N * 4,      N * 8,         N * 4,
+                            N * 4,     N * K * 32, N * K * 32, N * 48,     N * (size_t)std::max(max_boxes, 1) * 32};
+  size_t total = 0;
+  for (size_t b : sizes) total += align256(b);
+  if (c->work.ensure(total)) return -1;
+  char* p = c->work.as<char>();
+  void* ptrs[17];
+  for (int i = 0; i < 17; ++i) {
+    ptrs[i] = p;
+    p += align256(sizes[i]);
+  }
+  c->gray = (uint8_t*)ptrs[0];
+  c->mask = (uint8_t*)ptrs[1];
+  c->desc = (uint8_t*)ptrs[2];
+  c->inl = (uint8_t*)ptrs[3];
+  c->kps = (float*)ptrs[4];
+  c->cnt = (int32_t*)ptrs[5];
+  c->idx = (int32_t*)ptrs[6];
+  c->dist = (int32_t*)ptrs[7];
+  c->n_knn = (int32_t*)ptrs[8];
+  c->n_good = (int32_t*)ptrs[9];
+  c->info = (int32_t*)ptrs[10];
+  c->slots = (int32_t*)ptrs[11];
+  c->box_cnt = (int32_t*)ptrs[12];
+  c->tmp = (double*)ptrs[13];
+  c->good = (double*)ptrs[14];
+  c->warps = (double*)ptrs[15];
+  c->boxes = (double*)ptrs[16];
+  c->cap = n;
+  c->cap_boxes = max_boxes;
+  return 0;
+}
+
+mq::SiftWs* ctx_sift_ws(mq_ctx* ctx) {
+  if (!ctx->sift_ws) ctx->sift_ws = mq::sift_ws_create();
+  return ctx->sift_ws;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mq_cmc_preprocess(mq_ctx* ctx, const uint8_t* frames, int64_t frame_stride, int n_img, int height, int width,
+                      double scale, uint8_t* gray_out, void* stream) {
+  if (!ctx || !frames || !gray_out) return fail("mq_cmc_preprocess: null argument");
+  if (n_img < 0 || height < 2 || width < 2 || !(scale > 0.0) || scale > 1.0) return fail("mq_cmc_preprocess: bad dims");
+  HIP_TRY(hipSetDevice(ctx->device));
+  K_TRY(mq::cmc_preprocess(frames, frame_stride, n_img, height, width, scale, gray_out, (hipStream_t)stream));
+  return 0;
+}
+
+int mq_sift_detect(mq_ctx* ctx, const uint8_t* gray, int n_img, int height, int width, int first_octave,
+                   const uint8_t* mask, int max_kp, float* kps_out, int32_t* counts_out, float* dog_out,
+                   void* stream) {
+  if (!ctx || !gray || !kps_out || !counts_out) return fail("mq_sift_detect: null argument");
+  mq::SiftGeom g;
+  if (n_img < 0 || max_kp < 1 || max_kp > mq::CMC_KMAX || mq::sift_geometry(height, width, first_octave, &g))
+    return fail("mq_sift_detect: bad dims (first_octave -1 or 0, max_kp <= 2048)");
+  HIP_TRY(hipSetDevice(ctx->device));
+  K_TRY(mq::sift_detect(ctx_sift_ws(ctx), gray, n_img, height, width, first_octave, mask, max_kp, kps_out, counts_out,
+                        dog_out, (hipStream_t)stream));
+  return 0;
+}
+
+int mq_sift_describe(mq_ctx* ctx, const uint8_t* gray, int n_img, int height, int width, int first_octave,
+                     const float* kps, const int32_t* counts, int max_kp, uint8_t* desc_out, void* stream) {
+  if (!ctx || !gray || !kps || !counts || !desc_out) return fail("mq_sift_describe: null argument");
+  mq::SiftGeom g;
+  if (n_img < 0 || max_kp < 1 || max_kp > mq::CMC_KMAX || mq::sift_geometry(height, width, first_octave, &g))
+    return fail("mq_sift_describe: bad dims (first_octave -1 or 0, max_kp <= 2048)");
+  HIP_TRY(hipSetDevice(ctx->device));
+  K_TRY(mq::sift_describe(ctx_sift_ws(ctx), gray, n_img, height, width, first_octave, kps, counts, max_kp, desc_out,
+                          (hipStream_t)stream));
+  return 0;
+}
+
+int mq_desc_match_knn2(mq_ctx* ctx, const uint8_t* query, const int32_t* n_query, const uint8_t* train,
+                       const int32_t* n_train, int n_img, int max_kp, int32_t* idx_out, int32_t* dist_out,
+                       void* stream) {
+  if (!ctx || !query || !n_query || !train || !n_train || !idx_out || !dist_out)
+    return fail("mq_desc_match_knn2: null argument");
+  if (n_img < 0 || max_kp < 1 || max_kp > mq::CMC_KMAX) return fail("mq_desc_match_knn2: bad dims");
+  HIP_TRY(hipSetDevice(ctx->device));
+  K_TRY(mq::desc_match_knn2(query, n_query, nullptr, train, n_train, n_img, max_kp, idx_out, dist_out,
+                            (hipStream_t)stream));
+  return 0;
+}
+
+int mq_affine_partial_ransac(mq_ctx* ctx, const double* pts, const int32_t* counts, int n_sets, int max_pts,
+                             double threshold, double* warps_out, int32_t* info_out, uint8_t* mask_out, void* stream) {
+  if (!ctx || !pts || !counts || !warps_out || !info_out || !mask_out)
+    return fail("mq_affine_partial_ransac: null argument");
+  if (n_sets < 0 || max_pts < 1 || !(threshold > 0.0)) return fail("mq_affine_partial_ransac: bad dims");
+  HIP_TRY(hipSetDevice(ctx->device));
+  K_TRY(mq::affine_partial_ransac(pts, counts, n_sets, max_pts, threshold, warps_out, info_out, mask_out,
+                                  (hipStream_t)stream));
+  return 0;
+}
+
+int mq_cmc_create(mq_ctx* ctx, int n_slots, int height, int width, double scale, int max_kp, mq_cmc** out) {
+  if (!ctx || !out) return fail("mq_cmc_create: null argument");
+  if (n_slots < 1 || n_slots > 4096 || height < 2 || width < 2 || !(scale > 0.0) || scale > 1.0 || max_kp < 1 ||
+      max_kp > mq::CMC_KMAX)
+    return fail("mq_cmc_create: bad dims");
+  const int h = (int)std::nearbyint(height * scale), w = (int)std::nearbyint(width * scale);
+  mq::SiftGeom g;
+  if (mq::sift_geometry(h, w, -1, &g)) return fail("mq_cmc_create: scaled image too small or too large");
+  HIP_TRY(hipSetDevice(ctx->device));
+  mq_cmc* c = new mq_cmc();
+  c->ctx = ctx;
+  c->n_slots = n_slots;
+  c->H = height;
+  c->W = width;
+  c->h = h;
+  c->w = w;
+  c->scale = scale;
+  c->max_kp = max_kp;
+  c->ws = mq::sift_ws_create();
+  const size_t K = (size_t)max_kp;
+  if (hipMalloc((void**)&c->prev_kps, n_slots * K * 7 * sizeof(float)) != hipSuccess ||
+      hipMalloc((void**)&c->prev_desc, n_slots * K * 128) != hipSuccess ||
+      hipMalloc((void**)&c->prev_cnt, n_slots * sizeof(int32_t)) != hipSuccess ||
+      hipMemset(c->prev_cnt, 0, n_slots * sizeof(int32_t)) != hipSuccess) {
+    mq_cmc_destroy(c);
+    return fail("mq_cmc_create: out of device memory", -5);
+  }
+  *out = c;
+  return 0;
+}
+
+int mq_cmc_destroy(mq_cmc* cmc) {
+  if (!cmc) return 0;
+  (void)hipSetDevice(cmc->ctx->device);
+  mq::sift_ws_destroy(cmc->ws);
+  (void)hipFree(cmc->prev_kps);
+  (void)hipFree(cmc->prev_desc);
+  (void)hipFree(cmc->prev_cnt);
+  cmc->work.release();
+  delete cmc;
+  return 0;
+}
+
+int mq_cmc_reset(mq_cmc* cmc, int slot) {
+  if (!cmc) return fail("mq_cmc_reset: null argument");
+  if (slot < -1 || slot >= cmc->n_slots) return fail("mq_cmc_reset: bad slot");
+  HIP_TRY(hipSetDevice(cmc->ctx->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if (slot < 0)
+    HIP_TRY(hipMemset(cmc->prev_cnt, 0, cmc->n_slots * sizeof(int32_t)));
+  else
+    HIP_TRY(hipMemset(cmc->prev_cnt + slot, 0, sizeof(int32_t)));
+  return 0;
+}
+
+int mq_cmc_apply(mq_cmc* c, const uint8_t* frames, int64_t frame_stride, int n_img, const int32_t* slots,
+                 const double* boxes, const int32_t* box_counts, int max_boxes, double* warps_out, int32_t* stats_out,
+                 void* stream) {
+  if (!c || !frames || !slots || !warps_out) return fail("mq_cmc_apply: null argument");
+  if (n_img < 1 || n_img > c->n_slots || max_boxes < 0 || (max_boxes > 0 && (!boxes || !box_counts)))
+    return fail("mq_cmc_apply: bad dims");
+  for (int i = 0; i < n_img; ++i) {
+    if (slots[i] < 0 || slots[i] >= c->n_slots) return fail("mq_cmc_apply: bad slot");
+    for (int j = 0; j < i; ++j)
+      if (slots[j] == slots[i]) return fail("mq_cmc_apply: a slot appears twice in one call");
+  }
+  HIP_TRY(hipSetDevice(c->ctx->device));
+  if (cmc_reserve(c, n_img, max_boxes)) return fail("mq_cmc_apply: out of device memory", -5);
+  hipStream_t s = (hipStream_t)stream;
+  const int K = c->max_kp;
+  HIP_TRY(hipMemcpyAsync(c->slots, slots, n_img * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  if (max_boxes > 0) {
+    HIP_TRY(hipMemcpyAsync(c->boxes, boxes, (size_t)n_img * max_boxes * 4 * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c->box_cnt, box_counts, n_img * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  }
+  K_TRY(mq::cmc_preprocess(frames, frame_stride, n_img, c->H, c->W, c->scale, c->gray, s));
+  K_TRY(mq::cmc_mask(c->boxes, max_boxes > 0 ? c->box_cnt : nullptr, max_boxes, n_img, c->h, c->w, c->scale, c->mask, s));
+  K_TRY(mq::sift_detect(c->ws, c->gray, n_img, c->h, c->w, -1, c->mask, K, c->kps, c->cnt, nullptr, s));
+  K_TRY(mq::sift_describe(c->ws, nullptr, n_img, c->h, c->w, -1, c->kps, c->cnt, K, c->desc, s));
+  K_TRY(mq::desc_match_knn2(c->prev_desc, c->prev_cnt, c->slots, c->desc, c->cnt, n_img, K, c->idx, c->dist, s));
+  K_TRY(mq::cmc_match_filter(c->idx, c->dist, c->prev_kps, c->prev_cnt, c->slots, c->kps, c->cnt, n_img, K, c->h, c->w,
+                             c->tmp, c->good, c->n_knn, c->n_good, s));
+  K_TRY(mq::affine_partial_ransac(c->good, c->n_good, n_img, K, 3.0, c->warps, c->info, c->inl, s));
+  K_TRY(mq::cmc_store_prev(c->kps, c->desc, c->cnt, c->slots, n_img, K, c->prev_kps, c->prev_desc, c->prev_cnt, s));
+  // the one device -> host copy of the results: 6 doubles per image (+ the four counters when asked for)
+  std::vector<int32_t> cnt(n_img), knn(n_img), good(n_img), info(2 * n_img);
+  HIP_TRY(hipMemcpyAsync(warps_out, c->warps, (size_t)n_img * 6 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (stats_out) {
+    HIP_TRY(hipMemcpyAsync(cnt.data(), c->cnt, n_img * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(knn.data(), c->n_knn, n_img * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(good.data(), c->n_good, n_img * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(info.data(), c->info, 2 * n_img * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+  for (int i = 0; i < n_img; ++i) {
+    warps_out[6 * i + 2] /= c->scale;  // boxmot: H[0, 2] /= scale, H[1, 2] /= scale
+    warps_out[6 * i + 5] /= c->scale;
+    if (stats_out) {
+      stats_out[4 * i] = cnt[i];
+      stats_out[4 * i + 1] = knn[i];
+      stats_out[4 * i + 2] = good[i];
+      stats_out[4 * i + 3] = info[2 * i + 1];
+    }
+  }
   return 0;
 }
 

@@ -24,6 +24,8 @@ EXPORTED = [
     "mq_det_resize_patch", "mq_layernorm", "mq_add_layernorm", "mq_window_attention", "mq_patch_merge_gather", "mq_upsample_add",
     "mq_im2col3x3", "mq_conv3x3_bf16", "mq_gemm_resid_relu_bf16", "mq_id_conv_bf16", "mq_deconv_subpixel_pack", "mq_deconv_subpixel_bf16", "mq_f32_to_bf16", "mq_subsample2", "mq_nms", "mq_rpn_proposals", "mq_roi_align", "mq_rcnn_post", "mq_det_topk_boxes", "mq_optim_prepare", "mq_trust_region_2d", "mq_optim_points", "mq_attention_bf16", "mq_alldata_json",
     "mq_id_crop_resize", "mq_id_preprocess", "mq_id_im2col", "mq_id_maxpool", "mq_id_relu_bf16", "mq_id_head",
+    "mq_cmc_preprocess", "mq_sift_detect", "mq_sift_describe", "mq_desc_match_knn2", "mq_affine_partial_ransac",
+    "mq_cmc_create", "mq_cmc_destroy", "mq_cmc_reset", "mq_cmc_apply",
 ]
 
 
@@ -99,6 +101,15 @@ _SIGS = {
     "mq_trust_region_2d": (i32, [vp, vp, f64, vp]),
     "mq_viterbi_filter": (i32, [vp, vp, i32, i32, i32, i32, f64, i32, f64, vp, vp]),
     "mq_attention_bf16": (i32, [vp, vp, vp, i32, i32, i32, i32, vp]),
+    "mq_cmc_preprocess": (i32, [vp, vp, i64, i32, i32, i32, f64, vp, vp]),
+    "mq_sift_detect": (i32, [vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp]),
+    "mq_sift_describe": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp]),
+    "mq_desc_match_knn2": (i32, [vp, vp, vp, vp, vp, i32, i32, vp, vp, vp]),
+    "mq_affine_partial_ransac": (i32, [vp, vp, vp, i32, i32, f64, vp, vp, vp, vp]),
+    "mq_cmc_create": (i32, [vp, i32, i32, i32, f64, i32, C.POINTER(vp)]),
+    "mq_cmc_destroy": (i32, [vp]),
+    "mq_cmc_reset": (i32, [vp, i32]),
+    "mq_cmc_apply": (i32, [vp, vp, i64, i32, vp, vp, vp, i32, vp, vp, vp]),
     "mq_optim_points": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, vp, i32, i32, vp, f64, f64, f64, i32, i32, i32,
                               i32, f64, i32, vp, vp]),
 }

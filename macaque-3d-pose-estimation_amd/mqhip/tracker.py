@@ -22,9 +22,12 @@ Restated from boxmot's published BoT-SORT (boxmot is absent here):
 * output rows ``[x1, y1, x2, y2, id, conf, cls, det_ind]`` from the Kalman posterior of every
   activated track.
 
-Camera-motion compensation: the SIFT + RANSAC affine of boxmot needs OpenCV (absent here).  ``cmc``
-is a callable (img, dets) -> 2x3 warp; the default is the identity, which is what the estimate tends
-to for the reference's fixed cage cameras.  Parity with boxmot is unpinned.
+Camera-motion compensation: ``cmc`` is a callable (img, dets) -> 2x3 warp from the previous frame's to
+this frame's coordinates.  The default is the identity, which is what the estimate tends to for the
+reference's fixed cage cameras.  ``make_cmc("sift", height, width)`` gives boxmot's SIFT + partial-affine
+estimate restated on the GPU (``mqhip.cmc.SiftCmc``, csrc/cmc.hip: the SIFT structure of cv2 with a
+deterministic RANSAC hypothesis set instead of cv2's RNG); it is opt-in, and its parity with cv2 / boxmot
+is unpinned (neither is installed).
 """
 from __future__ import annotations
 
@@ -210,6 +213,19 @@ def remove_duplicate_stracks(sa, sb):
 
 def identity_cmc(img, dets):
     return np.eye(2, 3)
+
+
+def make_cmc(method, height=None, width=None, **kw):
+    """The ``cmc`` callable for boxmot's ``cmc_method``: None / "none" -> the identity, "sift" -> a
+    ``mqhip.cmc.SiftCmc(height, width, **kw)`` (GPU; no CPU fallback).  Anything else raises."""
+    if method is None or method == "none":
+        return identity_cmc
+    if method == "sift":
+        if height is None or width is None:
+            raise ValueError('make_cmc("sift") needs the frame height and width')
+        from .cmc import SiftCmc
+        return SiftCmc(height, width, **kw)
+    raise ValueError(f"unknown camera-motion compensation method {method!r} (None or 'sift')")
 
 
 class BotSort:

@@ -159,21 +159,36 @@ def classify_boxes(id_model, imgs, boxes_per_view):
     return id_model.classify(imgs, boxes_per_view)
 
 
-def init_tracker(cfg=None):
-    """step1:99 / :430 ``BotSort(**BOTSORT_CFG)`` -- one per camera (camera-motion compensation: identity,
-    see mqhip.tracker)."""
+def init_tracker(cfg=None, cmc=None):
+    """step1:99 / :430 ``BotSort(**BOTSORT_CFG)`` -- one per camera.  ``cmc``: the camera-motion compensation
+    callable (img, dets) -> 2x3 warp; None keeps the identity (see mqhip.tracker)."""
     from mqhip.tracker import BotSort
-    return BotSort(**(cfg or BOTSORT_CFG))
+    if cmc is None:
+        return BotSort(**(cfg or BOTSORT_CFG))
+    return BotSort(**dict(cfg or BOTSORT_CFG, cmc=cmc))
 
 
-def track_stores(detector, stores, T, score_thr=SCORE_THR, tracker_cfg=None):
+def track_stores(detector, stores, T, score_thr=SCORE_THR, tracker_cfg=None, cmc=None):
     """Detector -> tracker per camera over step 1's frame plan (step1:225-252): a frame whose detections are
     all <= score_thr gets no tracker update and no rows; otherwise ``tracker.update(dets6, img)`` with
-    dets6 = [boxes, scores, 0].  Returns per camera {frame_number: tracker rows (k, 8)}."""
+    dets6 = [boxes, scores, 0].  Returns per camera {frame_number: tracker rows (k, 8)}.
+    ``cmc``: None -> the identity warp; "sift" -> the reference's ``cmc_method='sift'`` on the GPU, every
+    camera a slot of one shared ``mqhip.cmc.SiftCmc`` sized from the stores' image shape."""
     dets = detect_stores(detector, stores, T, score_thr)
     out = []
+    shared = None
     for c, st in enumerate(stores):
-        tr = init_tracker(tracker_cfg)
+        cam_cmc = None
+        if cmc is not None:
+            if shared is None:
+                from mqhip.tracker import make_cmc
+                first = next((fn for fn, _, sc in dets[c] if len(sc)), None)
+                if first is not None:
+                    hh, ww = st.image(first).shape[:2]
+                    shared = make_cmc(cmc, hh, ww, n_slots=len(stores))
+            if shared is not None:
+                cam_cmc = shared.for_slot(c) if hasattr(shared, "for_slot") else shared
+        tr = init_tracker(tracker_cfg, cmc=cam_cmc)
         rows = {}
         for fn, b, sc in dets[c]:
             if len(sc) == 0:
@@ -822,7 +837,8 @@ def _write_step1_files(out_dirs, items, into):
 
 def step1_proc2d_custom(data_name, results_root, raw_root, fps=24.0, t_intv=None, redo=False, pose_model=None,
                         device_str="cuda:0", steps_per_batch=8, id_model=None, detector=None, world=1, rank=0,
-                        group=None, sharded=False, gather_device=None, background_writes=False, timings=None):
+                        group=None, sharded=False, gather_device=None, background_writes=False, timings=None,
+                        cmc=None):
     """step1_proc2d.py:389-447 with the frame stores of ``mqhip.io.FrameStore`` and the tracker
     rows they carry (or, with ``detector``, the detector -> tracker chain).  ``id_model``: see
     ``resolve_id_models`` ("auto" = the reference's per-camera variant).  Writes
@@ -835,7 +851,8 @@ def step1_proc2d_custom(data_name, results_root, raw_root, fps=24.0, t_intv=None
     RCCL, None for gloo); then rank r post-processes (KP_THR / EMA) and writes the cameras
     c = r (mod world) only.  The files equal the single-process ones bit for bit.
     ``background_writes``: the files are written by a thread (``Step1Output.wait()`` joins it) while the
-    caller goes on with the rows in memory."""
+    caller goes on with the rows in memory.  ``cmc``: the tracker's camera-motion compensation with
+    ``detector`` (None: identity; "sift": ``track_stores``)."""
     import glob
     import threading
     from mqhip.io import FrameStore
@@ -861,7 +878,7 @@ def step1_proc2d_custom(data_name, results_root, raw_root, fps=24.0, t_intv=None
     if pose_model is None:
         pose_model = init_pose_model(device=device_str)
     sel = [stores[i] for i in todo]
-    tracks = None if detector is None else track_stores(detector, sel, T)
+    tracks = None if detector is None else track_stores(detector, sel, T, cmc=cmc)
     id_models = resolve_id_models(sel, id_model, device_str)
     ids_sel = None
     if world > 1 or sharded:
@@ -892,11 +909,11 @@ def step1_proc2d_custom(data_name, results_root, raw_root, fps=24.0, t_intv=None
 
 
 def proc(data_name, results_root, raw_root, device_str="cuda:0", fps=24.0, pose_model=None, detector=None,
-         id_model="auto", **shard):
+         id_model="auto", cmc=None, **shard):
     """step1.proc (step1_proc2d.py:450) over every camera's frame store: pose and ID on the stores' tracker
     rows, or the full detector -> tracker -> pose -> ID chain with ``detector``.  ``id_model="auto"`` is the
     reference's rule (every camera classified by the ID model of its variant, step1:424-427); None keeps
     the stores' own ID predictions (``resolve_id_models``).  Unlike the reference (which hard-codes cuda:1,
     step1:50,421) the device argument is honoured."""
     return step1_proc2d_custom(data_name, results_root, raw_root, fps=fps, pose_model=pose_model,
-                               device_str=device_str, detector=detector, id_model=id_model, **shard)
+                               device_str=device_str, detector=detector, id_model=id_model, cmc=cmc, **shard)
