@@ -34,6 +34,8 @@
 //
 // Accumulation order per output element is the one of gemm256_kernel (K in ascending 32-deep
 // MFMA steps, then + bias, then the epilogue op), so both kernels give bit-identical results.
+// The walk is a tile loop around a K loop, and a tile's first K-step is an instance of its own whose
+// MFMAs start from an inline-constant zero C: the accumulators are never zeroed on the VALU.
 //
 // The tile geometry is a template (PPShape<WMF, WNF>: MFMA fragments per wave in M and N; phase split,
 // DMA issue plan and counted waits derived from it); the epilogue is written for WNF = 4 and the library
@@ -181,7 +183,8 @@ __device__ __forceinline__ int pp_slot_group(int w, int i) {
 }
 
 // Epilogue of one wave's (16 WMF) x (16 WNF) block: acc[i][j] holds C[m0 + wm*BM/2 + i*16 + (l & 15)]
-// [n0 + wn*16*WNF + j*16 + 4*(l >> 4) + e].  Zeroes the accumulators for the next tile.
+// [n0 + wn*16*WNF + j*16 + 4*(l >> 4) + e].  Leaves the accumulators as they are: the next tile's first K-step
+// starts its MFMAs from a zero C.
 //
 // Sub-pixel deconvolution (DECONV): GEMM row m = input pixel (img, y, x) and column n = class (py, px)
 // x C_out + co store to output pixel (img, 2y + py, 2x + px), channel co, of the NHWC (2H, 2W) image.
@@ -232,7 +235,6 @@ __device__ __forceinline__ void pp_epilogue(const GemmArgs& p, f32x4 (&acc)[S::W
       v[1] = acc[i][j][1] + bias[j].y;
       v[2] = acc[i][j][2] + bias[j].z;
       v[3] = acc[i][j][3] + bias[j].w;
-      acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
       if constexpr (EPI == EPI_GELU_BF16) {
         const f32x2 g0 = gelu_sig2((f32x2){v[0], v[1]}), g1 = gelu_sig2((f32x2){v[2], v[3]});
         v[0] = g0.x;
@@ -249,6 +251,21 @@ __device__ __forceinline__ void pp_epilogue(const GemmArgs& p, f32x4 (&acc)[S::W
     // 16-byte store per lane per pair; an odd last fragment stores its 4 columns (8 B) per lane
     const bool odd = (lane >> 4) & 1;
     const int nbase = nn - (odd ? 4 : 0);
+    // head-major output (kernels.hpp gemm_out_bf16): the head and the column in it of this lane's store column of
+    // each fragment pair, once per tile instead of two divisions per store
+    size_t hm_off[WNF / 2] = {};
+    if (EPI == EPI_BF16 && p.head_dim) {
+#pragma unroll
+      for (int jp = 0; jp + 1 < WNF; jp += 2) {
+        const int n = nb + (jp + (odd ? 1 : 0)) * 16 + nbase;
+        const int head = n / p.head_dim;
+        hm_off[jp >> 1] = (size_t)head * p.M * p.head_dim + (n - head * p.head_dim);
+      }
+    }
+    auto out_ptr = [&](bf16_t* crow_p, int m, int n, int jp) -> bf16_t* {
+      if (EPI == EPI_BF16 && p.head_dim) return (bf16_t*)p.C + hm_off[jp >> 1] + (size_t)m * p.head_dim;
+      return crow_p + n;
+    };
 #if PP_DIAG & 512  // all arithmetic first, then the 16 stores back to back
     uint4 ov[WMF][WNF / 2];
 #endif
@@ -282,8 +299,7 @@ __device__ __forceinline__ void pp_epilogue(const GemmArgs& p, f32x4 (&acc)[S::W
         (void)crow_p;
         ov[i][jp >> 1] = o;
 #else
-        if (full || (m < p.M && n < p.N))
-          *reinterpret_cast<uint4*>(EPI == EPI_BF16 && p.head_dim ? gemm_out_bf16(p, m, n) : crow_p + n) = o;
+        if (full || (m < p.M && n < p.N)) *reinterpret_cast<uint4*>(out_ptr(crow_p, m, n, jp)) = o;
 #endif
       }
     }
@@ -330,7 +346,6 @@ __device__ __forceinline__ void pp_epilogue(const GemmArgs& p, f32x4 (&acc)[S::W
             o.y += acc[i][j][1] + bias[j].y;
             o.z += acc[i][j][2] + bias[j].z;
             o.w += acc[i][j][3] + bias[j].w;
-            acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
             *reinterpret_cast<float4*>((float*)p.C + (size_t)m * p.ldc + nb + j * 16 + nn) = o;
           }
         }
@@ -346,7 +361,6 @@ __device__ __forceinline__ void pp_epilogue(const GemmArgs& p, f32x4 (&acc)[S::W
       const int n = nb + j * 16 + nn;
       const float v[4] = {acc[i][j][0] + bias[j].x, acc[i][j][1] + bias[j].y, acc[i][j][2] + bias[j].z,
                           acc[i][j][3] + bias[j].w};
-      acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
       if (m >= p.M || n >= p.N) continue;
       float4* c = reinterpret_cast<float4*>((float*)p.C + (size_t)m * p.ldc + n);
       if constexpr (EPI == EPI_RESID_F32) {
@@ -507,23 +521,25 @@ __global__ __launch_bounds__(PP_T, 2) void gemm_pp_kernel(GemmArgs p, int tiles_
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, MQ_LDS_LOCAL(bias_lds), 4, bias_off, 0, 0, 0);
   };
 
+  // never zeroed: the first K-step of every tile starts each fragment's MFMA chain from a zero C
   f32x4 acc[WMF][WNF];
-#pragma unroll
-  for (int i = 0; i < WMF; ++i)
-#pragma unroll
-    for (int j = 0; j < WNF; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   bf16x8 a[QM][2], b0[NA][2], b1[NB][2];
 
-  auto mfma_quadrant = [&](int qm, auto& bb, int jbase, auto nj) {
+  // fresh: the quadrant's first MFMA of every fragment (kk = 0) takes a literal zero C instead of the accumulator
+  auto mfma_quadrant = [&](auto fresh, int qm, auto& bb, int jbase, auto nj) {
     if constexpr (!(PP_DIAG & (4096 | 8192))) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
       for (int i = 0; i < QM; ++i)
 #pragma unroll
-        for (int j = 0; j < decltype(nj)::value; ++j)
-          acc[qm * QM + i][jbase + j] =
-              __builtin_amdgcn_mfma_f32_16x16x32_bf16(bb[j][kk], a[i][kk], acc[qm * QM + i][jbase + j], 0, 0, 0);
+        for (int j = 0; j < decltype(nj)::value; ++j) {
+          f32x4& c = acc[qm * QM + i][jbase + j];
+          if (decltype(fresh)::value && kk == 0)
+            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bb[j][kk], a[i][kk], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+          else
+            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bb[j][kk], a[i][kk], c, 0, 0, 0);
+        }
     if constexpr (!(PP_DIAG & (4096 | 8192))) __builtin_amdgcn_s_setprio(0);
   };
   using NAc = std::integral_constant<int, NA>;
@@ -577,7 +593,20 @@ __global__ __launch_bounds__(PP_T, 2) void gemm_pp_kernel(GemmArgs p, int tiles_
       pp_epilogue<EPI, S, MODE == PP_DECONV>(p, acc, reinterpret_cast<const float*>(bl), m0, n0, wm, wn, lane);
   };
   auto tile_full = [&](int m0, int n0) { return !(PP_DIAG & 48) && (m0 + S::BM <= p.M) && (n0 + S::BN <= p.N); };
-  for (int g = 0; g < total; ++g) {
+#define PP_LOOP_WAIT_E(n)                     \
+  do {                                        \
+    if (stores_pending)                       \
+      PP_LOOP_WAIT((n) + EPI_OPS);            \
+    else                                      \
+      PP_LOOP_WAIT(n);                        \
+  } while (0)
+  // One K-step (g-th of the walk; its stage is in slot g & 1).  The kernel holds two instances of it:
+  //   tile_start: the first K-step of a tile.  Every fragment's first MFMA takes a zero C, so nothing zeroes the
+  //     accumulators, and its first two waits allow for the stores of the epilogue before it.
+  //   steady: every other K-step.
+  auto kstep = [&](auto tile_start, int g) {
+    constexpr bool START = decltype(tile_start)::value;
+    using Fresh = std::integral_constant<bool, START>;
 #ifdef PP_STAMP
     stamp_g = g;
     if (g == PP_STAMP_G0) stamp_n = 0;
@@ -602,12 +631,12 @@ __global__ __launch_bounds__(PP_T, 2) void gemm_pp_kernel(GemmArgs p, int tiles_
     for (int i = 0; i < S::C0; ++i) issue(i, slot ^ 1);
     issue_bias();
     // retires the DMAs of the previous K-step's phase 2 (younger: its phase 3, this phase + bias)
-    if (stores_pending)
-      PP_LOOP_WAIT(S::N0 + EPI_OPS);
+    if constexpr (START)
+      PP_LOOP_WAIT_E(S::N0);
     else
       PP_LOOP_WAIT(S::N0);
     open_mfma();
-    mfma_quadrant(0, b0, 0, NAc{});
+    mfma_quadrant(Fresh{}, 0, b0, 0, NAc{});
     bar();
     // ---- phase 1: quadrant (M half 0, N part B)
 #pragma unroll
@@ -618,13 +647,14 @@ __global__ __launch_bounds__(PP_T, 2) void gemm_pp_kernel(GemmArgs p, int tiles_
 #pragma unroll
     for (int i = S::C0; i < S::C0 + S::C1; ++i) issue(i, slot ^ 1);
     // retires the previous K-step's phase-3 DMAs (younger: phase 0 + bias, this phase)
-    if (stores_pending)
-      PP_LOOP_WAIT(S::N1 + EPI_OPS);
-    else
+    if constexpr (START) {
+      PP_LOOP_WAIT_E(S::N1);
+      stores_pending = false;
+    } else {
       PP_LOOP_WAIT(S::N1);
-    stores_pending = false;
+    }
     open_mfma();
-    mfma_quadrant(0, b1, NA, NBc{});
+    mfma_quadrant(Fresh{}, 0, b1, NA, NBc{});
     bar();
     // ---- phase 2: quadrant (M half 1, N part A)
 #pragma unroll
@@ -635,7 +665,7 @@ __global__ __launch_bounds__(PP_T, 2) void gemm_pp_kernel(GemmArgs p, int tiles_
 #pragma unroll
     for (int i = S::C0 + S::C1; i < S::C0 + S::C1 + S::C2; ++i) issue(i, slot ^ 1);
     open_mfma();
-    mfma_quadrant(1, b0, 0, NAc{});
+    mfma_quadrant(Fresh{}, 1, b0, 0, NAc{});
     bar();
     // ---- phase 3: quadrant (M half 1, N part B)
 #pragma unroll
@@ -643,19 +673,21 @@ __global__ __launch_bounds__(PP_T, 2) void gemm_pp_kernel(GemmArgs p, int tiles_
     advance();
     PP_LOOP_WAIT(S::N3);  // phases 0-1 of this K-step (P0 of stage g+1) and the bias
     open_mfma();
-    mfma_quadrant(1, b1, NA, NBc{});
+    mfma_quadrant(Fresh{}, 1, b1, NA, NBc{});
     bar();
-    if (++kt == nk) {
-      epilogue(bias_lds, cm0, cn0);
-      stores_pending = tile_full(cm0, cn0);
-      kt = 0;
-      ++ct;
-      if (ct < my_tiles) {
-        pp_tile_coords<S>(lo + xb + ct * nbx, tiles_m, tiles_n, cm0, cn0);
-        bias_off = bias_offset(cn0);
-      }
+  };
+  int g = 0;
+  for (ct = 0; ct < my_tiles; ++ct) {
+    kstep(std::true_type{}, g++);
+    for (kt = 1; kt < nk; ++kt) kstep(std::false_type{}, g++);
+    epilogue(bias_lds, cm0, cn0);
+    stores_pending = tile_full(cm0, cn0);
+    if (ct + 1 < my_tiles) {
+      pp_tile_coords<S>(lo + xb + (ct + 1) * nbx, tiles_m, tiles_n, cm0, cn0);
+      bias_off = bias_offset(cn0);
     }
   }
+#undef PP_LOOP_WAIT_E
   if constexpr ((PP_DIAG & 16) != 0) {  // keep the accumulators live (a store the host never asks for)
     if (p.M < 0)
 #pragma unroll
