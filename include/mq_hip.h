@@ -373,6 +373,33 @@ int mq_triangulate_pinv(mq_ctx* ctx, const double* cams, int n_cams, const doubl
 int mq_geometry_affinity(mq_ctx* ctx, const double* cams, int n_cams, const double* points, const int32_t* cam_of_det,
                          int B, int M, int J, double thr_kp, double* affinity, void* stream);
 
+/* step-3 tracklet lift (step3_crossframematching.py calc_3dtrace :274-302, calc_p3d :1115-1130): one launch
+ * lifts n_cells (tracklet, frame) cells.
+ *   cams      : camera rows as for mq_omnidir_undistort (intrinsics) and mq_triangulate_pinv (R, t)
+ *   row_start : int32 (C, F + 1) CSR offsets of each camera's rows per frame
+ *   row_tid   : int32 (R) box id of each row
+ *   row_kp    : float64 (R, J, 3) x, y, score per joint (NaN x, y where step 1 wrote NaN), J <= 32
+ *   trk       : int32 (K, F, C) box id of tracklet k in camera c at frame f; negative = absent
+ *   cells     : int32 (n_cells, 2) the (k, f) cells
+ * Per cell and camera the last row of the frame carrying the box id; per joint the cameras whose x is not
+ * NaN and whose score is not below thr_kp (0.3 in step 3; calc_3dpose :262-268) are undistorted and solved
+ * by the pinv DLT when at least 2.
+ *   p3d    : optional float64 (n_cells, J, 3) (NULL to skip)
+ *   median : float64 (n_cells, 3) np.nanmedian over the joints;  mean: float64 (n_cells, 3) np.nanmean
+ * A cell with fewer than 2 non-negative trk entries gives NaN in p3d and median. */
+int mq_tracklet_traces(mq_ctx* ctx, const double* cams, int n_cams, const int32_t* row_start, const int32_t* row_tid,
+                       const double* row_kp, int n_rows, int n_frames, int n_joints, const int32_t* trk, int n_trk,
+                       const int32_t* cells, int n_cells, double thr_kp, double* p3d, double* median, double* mean,
+                       void* stream);
+
+/* step-3 ID votes (count_id_detections :839-870): votes int32 (n_cells, n_class) -- for every camera and every
+ * row carrying the cell's box id with row_score > conf_thr (0.8), one vote for row_cls (n_class <= 16;
+ * classes outside [0, n_class) are ignored).  row_cls int32 (R), row_score float64 (R); the rest as above. */
+int mq_tracklet_id_votes(mq_ctx* ctx, int n_cams, const int32_t* row_start, const int32_t* row_tid,
+                         const int32_t* row_cls, const double* row_score, int n_rows, int n_frames,
+                         const int32_t* trk, int n_trk, const int32_t* cells, int n_cells, double conf_thr,
+                         int n_class, int32_t* votes, void* stream);
+
 /* step-2 matchSVT (step2_crossviewmatching.py:130-216) batched over B keyframes:
  *   S          : float64 (B, Nmax, Nmax) affinity W of each keyframe (first n_det[b] rows / columns used)
  *   n_det      : int32 (B) detections per keyframe (0 = empty keyframe), Nmax <= 64

@@ -1193,6 +1193,40 @@ int mq_geometry_affinity(mq_ctx* ctx, const double* cams, int C, const double* p
   return 0;
 }
 
+int mq_tracklet_traces(mq_ctx* ctx, const double* cams, int C, const int32_t* row_start, const int32_t* row_tid,
+                       const double* row_kp, int n_rows, int n_frames, int n_joints, const int32_t* trk, int n_trk,
+                       const int32_t* cells, int n_cells, double thr_kp, double* p3d, double* median, double* mean,
+                       void* stream) {
+  int rc = check_geo(ctx, cams, C, n_cells);
+  if (rc) return rc;
+  if (n_cells == 0) return 0;
+  if (!row_start || !trk || !cells || !median || !mean) return fail("mq_tracklet_traces: null argument");
+  if (n_rows < 0 || n_frames <= 0 || n_trk <= 0) return fail("mq_tracklet_traces: bad sizes", -2);
+  if (n_rows > 0 && (!row_tid || !row_kp)) return fail("mq_tracklet_traces: null rows");
+  if (n_joints < 1 || n_joints > 32) return fail("mq_tracklet_traces: n_joints must be in [1, 32]", -2);
+  K_TRY(mq::tracklet_traces(cams, C, row_start, row_tid, row_kp, n_rows, n_frames, n_joints, trk, n_trk, cells,
+                            n_cells, thr_kp, p3d, median, mean, (hipStream_t)stream));
+  return 0;
+}
+
+int mq_tracklet_id_votes(mq_ctx* ctx, int C, const int32_t* row_start, const int32_t* row_tid,
+                         const int32_t* row_cls, const double* row_score, int n_rows, int n_frames,
+                         const int32_t* trk, int n_trk, const int32_t* cells, int n_cells, double conf_thr,
+                         int n_class, int32_t* votes, void* stream) {
+  if (!ctx) return fail("null ctx");
+  if (C <= 0 || C > 16) return fail("n_cams must be in [1, 16]", -2);
+  if (n_cells < 0) return fail("negative n", -2);
+  if (hipSetDevice(ctx->device) != hipSuccess) return fail("hipSetDevice failed", -5);
+  if (n_cells == 0) return 0;
+  if (!row_start || !trk || !cells || !votes) return fail("mq_tracklet_id_votes: null argument");
+  if (n_rows < 0 || n_frames <= 0 || n_trk <= 0) return fail("mq_tracklet_id_votes: bad sizes", -2);
+  if (n_rows > 0 && (!row_tid || !row_cls || !row_score)) return fail("mq_tracklet_id_votes: null rows");
+  if (n_class < 1 || n_class > 16) return fail("mq_tracklet_id_votes: n_class must be in [1, 16]", -2);
+  K_TRY(mq::tracklet_id_votes(C, row_start, row_tid, row_cls, row_score, n_rows, n_frames, trk, n_trk, cells,
+                              n_cells, conf_thr, n_class, votes, (hipStream_t)stream));
+  return 0;
+}
+
 int mq_match_svt(mq_ctx* ctx, const double* S, const int32_t* n_det, const int32_t* cam_of_det, int B, int Nmax,
                  double alpha, double lambda, double mu, double tol, int max_iter, int pselect, uint8_t* match,
                  double* x_out, int32_t* iters, void* stream) {

@@ -22,4 +22,11 @@ int match_svt(const double* S, const int32_t* n_det, const int32_t* cam_of_det, 
               double lambda, double mu, double tol, int max_iter, int pselect, void* ws, uint8_t* match,
               double* x_out, int32_t* iters, hipStream_t s);
 size_t match_svt_workspace_bytes(int B, int Nmax);
+// step-3 tracklet lift (tracklet.hip)
+int tracklet_traces(const double* cams, int C, const int32_t* row_start, const int32_t* row_tid,
+                    const double* row_kp, int R, int F, int J, const int32_t* trk, int K, const int32_t* cells,
+                    int N, double thr_kp, double* p3d, double* median, double* mean, hipStream_t s);
+int tracklet_id_votes(int C, const int32_t* row_start, const int32_t* row_tid, const int32_t* row_cls,
+                      const double* row_score, int R, int F, const int32_t* trk, int K, const int32_t* cells, int N,
+                      double conf_thr, int n_class, int32_t* votes, hipStream_t s);
 }  // namespace mq

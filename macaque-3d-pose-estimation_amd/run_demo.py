@@ -9,9 +9,12 @@ This build runs the same chain on MI355X with the parts outside its scope replac
 * step 1 (``src.pipeline.step1_proc2d.proc``): the pose slice over every camera's frame store
   and the ID classifier of each camera's variant; the detector / tracker output arrives as the
   stores' tracker rows;
-* steps 2-3: association is bypassed -- ``kp2d.pickle`` is written by step 3's own
+* steps 2-3: by default association is bypassed -- ``kp2d.pickle`` is written by step 3's own
   ``create_kp2dfile`` from a known track -> individual map
-  (``src.pipeline.step3_crossframematching.proc_known_assignment``);
+  (``src.pipeline.step3_crossframematching.proc_known_assignment``); with ``association="match"``
+  (``--association match``) the reference's chain runs instead: ``step2.proc`` (cross-view matching at the
+  keyframes -> ``match_keyframe.pickle``) and ``step3.proc`` (tracklets, stitching, ID votes ->
+  ``kp2d.pickle``, ``track.pickle``, ``collar_id.pickle``), on rank 0 from the files step 1 wrote;
 * step 4 (``src.pipeline.step4_aniposefiltering.proc``): unchanged drop-in;
 * visualisation (video rendering) is out of scope and the ``pictorial`` import is not needed.
 
@@ -29,16 +32,22 @@ import argparse
 import os
 
 from src.pipeline import step1_proc2d as step1
+from src.pipeline import step2_crossviewmatching as step2
 from src.pipeline import step3_crossframematching as step3
 from src.pipeline import step4_aniposefiltering as step4
 
 
 def proc(data_name, fps, results_dir_root, device_str, config_path, raw_data_dir, n_kp, vidfile_prefix='',
          n_animal=4, track_to_animal=None, pose_model=None, id_model="auto", world=1, rank=0, group=None,
-         sharded=False, gather_device=None, timings=None):
+         sharded=False, gather_device=None, timings=None, association="known"):
     """run_demo.py:21-30: step 1 -> (known assignment) -> step 4; returns step 4's kp3d dict (on rank 0;
     None on the other ranks of a sharded run).  ``timings``: optional dict filled with wall seconds per
     stage.
+
+    ``association``: "known" (default) maps track ids to individuals directly (``track_to_animal``);
+    "match" runs the reference's association instead -- step 2 (``match_keyframe.pickle``) and step 3
+    (tracklets, stitching, ID votes -> ``kp2d.pickle``) on rank 0 from the files step 1 wrote, then step 4 on
+    rank 0; the other ranks of a sharded run wait at the barrier and return None.
 
     Steps 3-4 take step 1's rows in memory (the files are still written, by a background thread joined
     before returning).  On a sharded run (``world`` > 1 or ``sharded``) rank r post-processes and writes
@@ -54,11 +63,14 @@ def proc(data_name, fps, results_dir_root, device_str, config_path, raw_data_dir
                        id_model=id_model, world=world, rank=rank, group=group, sharded=sharded,
                        gather_device=gather_device, background_writes=True, timings=timings)
     t1 = time.perf_counter()
+    if association not in ("known", "match"):
+        raise ValueError(f"association must be 'known' or 'match', got {association!r}")
     try:
-        kp2d = step3.kp2d_from_step1(s1out, step3.camera_ids(config_path), n_animal=n_animal, n_kp=n_kp,
-                                     track_to_animal=track_to_animal, world=world if (world > 1 or sharded) else 1,
-                                     group=group if (world > 1 or sharded) else None,
-                                     device=gather_device if (world > 1 or sharded) else None)
+        kp2d = None if association == "match" else step3.kp2d_from_step1(
+            s1out, step3.camera_ids(config_path), n_animal=n_animal, n_kp=n_kp,
+            track_to_animal=track_to_animal, world=world if (world > 1 or sharded) else 1,
+            group=group if (world > 1 or sharded) else None,
+            device=gather_device if (world > 1 or sharded) else None)
         t2 = time.perf_counter()
         sharded_run = world > 1 or sharded
         if kp2d is None and sharded_run:
@@ -77,8 +89,15 @@ def proc(data_name, fps, results_dir_root, device_str, config_path, raw_data_dir
         if kp2d is None:
             if s1out is not None:
                 s1out.wait()               # the files are the input of the file path
-            kp2d = step3.proc_known_assignment(data_name, results_dir_root, config_path, n_animal=n_animal,
-                                               n_kp=n_kp, track_to_animal=track_to_animal)
+            if association == "match":
+                from mqhip import io as mqio
+                step2.proc(data_name, results_dir_root, raw_data_dir, config_path, device=device)
+                step3.proc(data_name, results_dir_root, raw_data_dir, config_path, n_animal=n_animal, n_kp=n_kp,
+                           device=device)
+                kp2d = mqio.load_array_pickle(os.path.join(result_dir, "kp2d.pickle"))
+            else:
+                kp2d = step3.proc_known_assignment(data_name, results_dir_root, config_path, n_animal=n_animal,
+                                                   n_kp=n_kp, track_to_animal=track_to_animal)
         elif rank == 0:
             from mqhip import io as mqio
             os.makedirs(result_dir, exist_ok=True)
@@ -142,10 +161,12 @@ if __name__ == '__main__':
     ap.add_argument("--config", default="./calib/config.yaml")
     ap.add_argument("--raw", default="./videos")
     ap.add_argument("--n-kp", type=int, default=17)
+    ap.add_argument("--association", choices=("known", "match"), default="known",
+                    help="known: track id -> individual map; match: steps 2-3 (cross-view / cross-frame matching)")
     a = ap.parse_args()
     W, R, L, G, dev = _dist_from_env()
     proc(a.data, a.fps, a.results, f"cuda:{L}", a.config, a.raw, a.n_kp, world=W, rank=R, group=G,
-         gather_device=dev)
+         gather_device=dev, association=a.association)
     if W > 1:
         import torch.distributed as dist
         dist.barrier()
