@@ -537,6 +537,43 @@ int mq_cmc_apply(mq_cmc* cmc, const uint8_t* frames, int64_t frame_stride, int n
                  const double* boxes, const int32_t* box_counts, int max_boxes, double* warps_out, int32_t* stats_out,
                  void* stream);
 
+/* ---- Pose overlay (csrc/overlay.hip): the reference's last stage, src/pipeline/visualize_result.py (and
+ * visualize_result_2.py), from kp3d to the drawn frame.  tests/overlay_ref.py is the numpy restatement; the
+ * coverage rules are this project's own and exact (overlay.hip's head), cv2 parity of the edges is unpinned.
+ *
+ * The skeleton (host arrays): pairs int32 (n_pairs, 2) joint slots of each limb (draw_kps' kp_con, :73-93),
+ * radius int32 (n_joints + 1) disc radius per slot (:102-105; mrksize, eyes mrksize + 1), joint_flags int32
+ * (n_joints + 1): bit 0 draw the disc, bit 1 the joint is set to None before drawing (visualize_result_2.py's
+ * clean_kp :39-41: no disc and no limb).  Slot n_joints is the neck.  n_joints >= 7, n_animals in [1, 8],
+ * n_joints + 1 + n_pairs <= 64. */
+
+/* Primitive tables of n_img output images (visualize_result.py proc :220-242, clean_kp :30-51, the geometry
+ * of draw_kps :100-110 and ellipse_line :19-25):
+ *   cam_of_img : int32 (n_img) camera row of each image (outside [0, n_cams): nothing is drawn)
+ *   kp3d       : float64 (n_img, n_animals, n_joints, 3);  score: float64 (n_img, n_animals, n_joints)
+ *   prim_i     : int32 (n_img, n_animals, n_joints + 1 + n_pairs, 8) per slot [valid, cx, cy, r, x0, y0, x1, y1]:
+ *                disc slots first (centre from int(), radius), then limb slots (cx = cy = r = 0); x0..y1 is the
+ *                inclusive bounding box; an invalid slot is all zero
+ *   prim_d     : float64 (n_img, n_animals, n_pairs, 4) limb end points x1, y1, x2, y2 as projected (0 if invalid)
+ * The neck is the mean of joints 5 and 6 in 3D and of their scores; a joint is dropped when no joint of the
+ * animal has (X != 0) & (score > 0), when its projected x (or y) is NaN, or outside (-1000, 3000) on an axis. */
+int mq_overlay_primitives(mq_ctx* ctx, const double* cams, int n_cams, const int32_t* cam_of_img, const double* kp3d,
+                          const double* score, int n_img, int n_animals, int n_joints, const int32_t* pairs,
+                          int n_pairs, const int32_t* radius, const int32_t* joint_flags, int mrksize,
+                          int32_t* prim_i, double* prim_d, void* stream);
+
+/* mq_overlay_primitives, then the fused copy + draw (copy.deepcopy(frame) :218, draw_kps per animal :239-242,
+ * cv2.circle / cv2.ellipse thickness -1): out uint8 (n_img, height, width, 3) BGR, image b drawn over
+ * frames + src_index[b] * frame_stride (bytes; frames holds n_src images, several outputs may share one; an
+ * index outside [0, n_src) reads as black).  out must not overlap frames.  Colours (255,0,0), (0,255,0),
+ * (0,0,255), (255,255,255) for animals 0..3, black from 4 (:191, :239-242); a pixel takes the highest animal
+ * index covering it.  prim_i / prim_d as above (outputs, and the draw kernel's input). */
+int mq_overlay_render(mq_ctx* ctx, const double* cams, int n_cams, const int32_t* cam_of_img, const double* kp3d,
+                      const double* score, int n_img, int n_animals, int n_joints, const int32_t* pairs, int n_pairs,
+                      const int32_t* radius, const int32_t* joint_flags, int mrksize, const uint8_t* frames,
+                      int64_t frame_stride, int n_src, const int32_t* src_index, int height, int width,
+                      int32_t* prim_i, double* prim_d, uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,7 @@
 
 #include "cmc.hpp"
 #include "geometry.hpp"
+#include "overlay.hpp"
 #include "detector.hpp"
 #include "idcls.hpp"
 #include "kernels.hpp"
@@ -1543,6 +1544,73 @@ int mq_cmc_apply(mq_cmc* c, const uint8_t* frames, int64_t frame_stride, int n_i
       stats_out[4 * i + 3] = info[2 * i + 1];
     }
   }
+  return 0;
+}
+
+// ----------------------------------------------------------------------------- pose overlay
+static int overlay_skeleton(const char* who, int A, int J, const int32_t* pairs, int P, const int32_t* radius,
+                            const int32_t* joint_flags, int mrksize, mq::OverlaySkeleton& sk) {
+  const std::string w(who);
+  if (A < 1 || A > mq::OVL_MAX_ANIMALS) return fail(w + ": n_animals must be in [1, 8]", -2);
+  if (J < 7) return fail(w + ": n_joints must be >= 7 (the neck is the mean of joints 5 and 6)", -2);
+  if (P < 0 || J + 1 + P > mq::OVL_MAX_PRIMS)
+    return fail(w + ": n_joints + 1 + n_pairs must be <= 64 primitives per animal", -2);
+  if (!radius || !joint_flags || (P > 0 && !pairs)) return fail(w + ": null skeleton");
+  if (mrksize < 0 || mrksize > 255) return fail(w + ": mrksize must be in [0, 255]", -2);
+  std::memset(&sk, 0, sizeof(sk));
+  sk.n_pairs = P;
+  for (int p = 0; p < P; ++p) {
+    const int a = pairs[2 * p], b = pairs[2 * p + 1];
+    if (a < 0 || a > J || b < 0 || b > J) return fail(w + ": pair joint outside [0, n_joints]", -2);
+    sk.pair_a[p] = (uint8_t)a;
+    sk.pair_b[p] = (uint8_t)b;
+  }
+  for (int j = 0; j <= J; ++j) {
+    if (radius[j] < 0 || radius[j] > 255) return fail(w + ": radius must be in [0, 255]", -2);
+    if (joint_flags[j] & ~3) return fail(w + ": unknown joint flag", -2);
+    sk.radius[j] = (uint8_t)radius[j];
+    sk.flags[j] = (uint8_t)joint_flags[j];
+  }
+  return 0;
+}
+
+int mq_overlay_primitives(mq_ctx* ctx, const double* cams, int C, const int32_t* cam_of_img, const double* kp3d,
+                          const double* score, int n_img, int A, int J, const int32_t* pairs, int P,
+                          const int32_t* radius, const int32_t* joint_flags, int mrksize, int32_t* prim_i,
+                          double* prim_d, void* stream) {
+  int rc = check_geo(ctx, cams, C, n_img);
+  if (rc) return rc;
+  mq::OverlaySkeleton sk;
+  if ((rc = overlay_skeleton("mq_overlay_primitives", A, J, pairs, P, radius, joint_flags, mrksize, sk))) return rc;
+  if (n_img == 0) return 0;
+  if (n_img > 65535) return fail("mq_overlay_primitives: at most 65535 images per call", -2);
+  if (!cam_of_img || !kp3d || !score || !prim_i || (P > 0 && !prim_d))
+    return fail("mq_overlay_primitives: null argument");
+  K_TRY(mq::overlay_primitives(cams, C, cam_of_img, kp3d, score, n_img, A, J, sk, mrksize, prim_i, prim_d,
+                               (hipStream_t)stream));
+  return 0;
+}
+
+int mq_overlay_render(mq_ctx* ctx, const double* cams, int C, const int32_t* cam_of_img, const double* kp3d,
+                      const double* score, int n_img, int A, int J, const int32_t* pairs, int P,
+                      const int32_t* radius, const int32_t* joint_flags, int mrksize, const uint8_t* frames,
+                      int64_t frame_stride, int n_src, const int32_t* src_index, int height, int width,
+                      int32_t* prim_i, double* prim_d, uint8_t* out, void* stream) {
+  if (height <= 0 || width <= 0 || width > (1 << 24) || height > (1 << 24))
+    return fail("mq_overlay_render: bad image size", -2);
+  const int64_t img_bytes = (int64_t)height * width * 3;
+  if (n_src <= 0 || frame_stride < img_bytes) return fail("mq_overlay_render: bad frame pool", -2);
+  if (n_img > 0) {
+    if (!frames || !src_index || !out) return fail("mq_overlay_render: null argument");
+    const uint8_t* f_end = frames + (size_t)(n_src - 1) * (size_t)frame_stride + img_bytes;
+    const uint8_t* o_end = out + (size_t)n_img * (size_t)img_bytes;
+    if (frames < o_end && out < f_end) return fail("mq_overlay_render: out overlaps frames (no in-place drawing)", -2);
+  }
+  int rc = mq_overlay_primitives(ctx, cams, C, cam_of_img, kp3d, score, n_img, A, J, pairs, P, radius, joint_flags,
+                                 mrksize, prim_i, prim_d, stream);
+  if (rc || n_img == 0) return rc;
+  K_TRY(mq::overlay_draw(frames, frame_stride, n_src, src_index, n_img, height, width, A, J, P, mrksize, prim_i,
+                         prim_d, out, (hipStream_t)stream));
   return 0;
 }
 

@@ -27,6 +27,7 @@ EXPORTED = [
     "mq_cmc_preprocess", "mq_sift_detect", "mq_sift_describe", "mq_desc_match_knn2", "mq_affine_partial_ransac",
     "mq_cmc_create", "mq_cmc_destroy", "mq_cmc_reset", "mq_cmc_apply",
     "mq_tracklet_traces", "mq_tracklet_id_votes",
+    "mq_overlay_primitives", "mq_overlay_render",
 ]
 
 
@@ -113,6 +114,9 @@ _SIGS = {
     "mq_cmc_apply": (i32, [vp, vp, i64, i32, vp, vp, vp, i32, vp, vp, vp]),
     "mq_tracklet_traces": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, i32, vp, i32, f64, vp, vp, vp, vp]),
     "mq_tracklet_id_votes": (i32, [vp, i32, vp, vp, vp, vp, i32, i32, vp, i32, vp, i32, f64, i32, vp, vp]),
+    "mq_overlay_primitives": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, i32, vp, vp, vp]),
+    "mq_overlay_render": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, i32, vp, i64, i32, vp, i32, i32,
+                                vp, vp, vp, vp]),
     "mq_optim_points": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, vp, i32, i32, vp, f64, f64, f64, i32, i32, i32,
                               i32, f64, i32, vp, vp]),
 }

@@ -180,3 +180,47 @@ def write_frame_store(directory, frames, frame_time, frame_number, tracks, camer
             json.dump(id_preds, f)
     if frame_index is not None:
         np.save(os.path.join(directory, "frame_index.npy"), np.asarray(frame_index, dtype=np.int64))
+
+
+class FrameStoreWriter:
+    """Write a FrameStore directory batch by batch: ``frames.npy`` is created at its final size with
+    ``np.lib.format.open_memmap`` and filled by ``append``, so a clip larger than memory streams through.
+    The tracker rows are empty.  ``metadata.yaml`` -- the file whose presence makes the directory a store -- is
+    written by ``close`` only, after every announced frame has arrived."""
+
+    def __init__(self, directory, n_frames, height, width, camera_id):
+        os.makedirs(directory, exist_ok=True)
+        self.directory, self.camera_id = str(directory), camera_id
+        self.n, self.pos = int(n_frames), 0
+        self.shape = (int(height), int(width), 3)
+        self.frames = np.lib.format.open_memmap(os.path.join(directory, "frames.npy"), mode="w+", dtype=np.uint8,
+                                                shape=(self.n,) + self.shape)
+        self.frame_number = np.zeros(self.n, dtype=np.int64)
+        self.frame_time = np.zeros(self.n, dtype=np.float64)
+
+    def append(self, frames, frame_number, frame_time):
+        frames = np.asarray(frames)
+        k = len(frames)
+        if frames.dtype != np.uint8 or frames.shape[1:] != self.shape:
+            raise ValueError(f"frames must be uint8 (k,) + {self.shape}, got {frames.dtype} {frames.shape}")
+        if self.pos + k > self.n or len(frame_number) != k or len(frame_time) != k:
+            raise ValueError("more frames than announced, or numbers / times of another length")
+        self.frames[self.pos:self.pos + k] = frames
+        self.frame_number[self.pos:self.pos + k] = frame_number
+        self.frame_time[self.pos:self.pos + k] = frame_time
+        self.pos += k
+
+    def close(self):
+        import yaml
+        if self.pos != self.n:
+            raise ValueError(f"{self.directory}: {self.pos} of {self.n} announced frames were written")
+        self.frames.flush()
+        del self.frames
+        d = self.directory
+        np.save(os.path.join(d, "frame_time.npy"), self.frame_time)
+        np.save(os.path.join(d, "frame_number.npy"), self.frame_number)
+        with open(os.path.join(d, "tracks.json"), "w") as f:
+            json.dump([[] for _ in range(self.n)], f)
+        with open(os.path.join(d, "metadata.yaml"), "w") as f:
+            yaml.safe_dump({"__store": {"camera_id": str(self.camera_id), "imgshape": list(self.shape),
+                                        "format": "npy"}}, f)

@@ -16,7 +16,10 @@ This build runs the same chain on MI355X with the parts outside its scope replac
   keyframes -> ``match_keyframe.pickle``) and ``step3.proc`` (tracklets, stitching, ID votes ->
   ``kp2d.pickle``, ``track.pickle``, ``collar_id.pickle``), on rank 0 from the files step 1 wrote;
 * step 4 (``src.pipeline.step4_aniposefiltering.proc``): unchanged drop-in;
-* visualisation (video rendering) is out of scope and the ``pictorial`` import is not needed.
+* visualisation (``src.pipeline.visualize_result.proc``, run_demo.py:33-39): opt-in through ``visualize``
+  (``--visualize all`` or ``--visualize 0,3``); rank 0 renders the listed cameras on the GPU after step 4 into
+  ``<out_dir>/<data>_<camid>/`` frame stores (no video codec exists in this build).  The
+  default leaves the chain at ``kp3d.pickle``.  The ``pictorial`` import is not needed.
 
 Multi-GPU (BASELINE config 3): run one process per GPU under ``torch.distributed.run``; every rank
 calls ``proc(..., world=W, rank=r, group=g)``.  Step 1's time steps are sharded over the ranks with
@@ -39,7 +42,8 @@ from src.pipeline import step4_aniposefiltering as step4
 
 def proc(data_name, fps, results_dir_root, device_str, config_path, raw_data_dir, n_kp, vidfile_prefix='',
          n_animal=4, track_to_animal=None, pose_model=None, id_model="auto", world=1, rank=0, group=None,
-         sharded=False, gather_device=None, timings=None, association="known"):
+         sharded=False, gather_device=None, timings=None, association="known", visualize=None,
+         out_dir='./output'):
     """run_demo.py:21-30: step 1 -> (known assignment) -> step 4; returns step 4's kp3d dict (on rank 0;
     None on the other ranks of a sharded run).  ``timings``: optional dict filled with wall seconds per
     stage.
@@ -48,6 +52,10 @@ def proc(data_name, fps, results_dir_root, device_str, config_path, raw_data_dir
     "match" runs the reference's association instead -- step 2 (``match_keyframe.pickle``) and step 3
     (tracklets, stitching, ID votes -> ``kp2d.pickle``) on rank 0 from the files step 1 wrote, then step 4 on
     rank 0; the other ranks of a sharded run wait at the barrier and return None.
+
+    ``visualize``: None (default: nothing is rendered, no output directory is made), "all" (every camera of
+    ``camera_id``, as run_demo.py:33-39) or a list of camera indices; rank 0 renders them after step 4 into
+    ``out_dir`` (``src.pipeline.visualize_result.proc``).
 
     Steps 3-4 take step 1's rows in memory (the files are still written, by a background thread joined
     before returning).  On a sharded run (``world`` > 1 or ``sharded``) rank r post-processes and writes
@@ -106,6 +114,13 @@ def proc(data_name, fps, results_dir_root, device_str, config_path, raw_data_dir
         out = step4.proc(data_name, results_dir_root, config_path, n_kp, redo=True, device=device, kp2d=kp2d,
                          world=world if split else 1, rank=rank if split else 0, group=group if split else None)
         t4 = time.perf_counter()
+        if visualize is not None:
+            if s1out is not None:
+                s1out.wait()               # frame_num.npy comes from step 1's background writer
+            if split:
+                _barrier(group)            # ... of the rank that owns the camera: every rank has joined its writer
+        if visualize is not None and rank == 0:
+            _visualize(visualize, data_name, config_path, raw_data_dir, results_dir_root, out_dir, device)
     finally:
         if s1out is not None:
             s1out.wait()
@@ -116,6 +131,19 @@ def proc(data_name, fps, results_dir_root, device_str, config_path, raw_data_dir
         if "gather_end" in timings:   # the sharded path: rank 0's timeline after the keypoint all-gather
             timings["after_gather_s"] = t4 - timings.pop("gather_end")
     return out
+
+
+def _visualize(visualize, data_name, config_path, raw_data_dir, results_dir_root, out_dir, device):
+    """run_demo.py:33-39: one ``vis.proc`` per camera (every camera of ``camera_id`` for "all")."""
+    import yaml
+    from src.pipeline import visualize_result as vis
+    with open(config_path, 'r') as f:
+        ID = yaml.safe_load(f)['camera_id']
+    cams = range(len(ID)) if isinstance(visualize, str) and visualize == "all" else [int(i) for i in visualize]
+    for i_cam in cams:
+        print(f"[INFO] Generating overlay frames for camera {ID[i_cam]} (index {i_cam}) ...")
+        vis.proc(data_name, i_cam, config_path, raw_data_dir, results_dir_root=results_dir_root, out_dir=out_dir,
+                 device=device)
 
 
 def _barrier(group):
@@ -163,10 +191,15 @@ if __name__ == '__main__':
     ap.add_argument("--n-kp", type=int, default=17)
     ap.add_argument("--association", choices=("known", "match"), default="known",
                     help="known: track id -> individual map; match: steps 2-3 (cross-view / cross-frame matching)")
+    ap.add_argument("--visualize", default=None,
+                    help="all, or camera indices i,j,...: render overlay frame stores after step 4 (default: none)")
+    ap.add_argument("--out", default="./output", help="where --visualize writes <data>_<camid>/")
     a = ap.parse_args()
+    vis_arg = None if a.visualize is None else ("all" if a.visualize == "all" else
+                                                [int(i) for i in a.visualize.split(",")])
     W, R, L, G, dev = _dist_from_env()
     proc(a.data, a.fps, a.results, f"cuda:{L}", a.config, a.raw, a.n_kp, world=W, rank=R, group=G,
-         gather_device=dev, association=a.association)
+         gather_device=dev, association=a.association, visualize=vis_arg, out_dir=a.out)
     if W > 1:
         import torch.distributed as dist
         dist.barrier()

@@ -1,0 +1,112 @@
+"""visualize_result.proc mirror (reference src/pipeline/visualize_result.py:136-254): reproject kp3d into one
+camera, draw every animal's skeleton over the camera's frames, and write the result.
+
+The drawing runs on the GPU (``mqhip.overlay.OverlayRenderer``: ``mq_overlay_render``, csrc/overlay.hip).
+Deviations from the reference, all stated in DESIGN.md section 8.5:
+
+* no video codec exists in this build (no cv2 / imageio / imgstore), so where the reference writes
+  ``<out>/<data>_<camid>.mp4`` this writes a frame store ``<out>/<data>_<camid>/`` that ``mqhip.io.FrameStore``
+  opens (``frames.npy`` uint8 (N, H, W, 3) BGR, ``frame_number.npy``, ``frame_time.npy``, ``metadata.yaml``, empty
+  ``tracks.json`` rows);
+* the discs and limbs are covered by the project's own exact rules, not by cv2's fixed-point rasterisers, and the
+  limb angle is not rounded to whole degrees: edges may differ from cv2's by a pixel;
+* the cameras come from ``<result>/calibration.toml`` (what step 4 writes and reads), not from the h5 files.
+
+Kept from the reference: ``kp3d_fxdJointLen.pickle`` is preferred over ``kp3d.pickle`` (:150-156), the "already
+exists" (:146-148) and "no kp3d file" (:154-156) early returns, the frame lookup through
+``<result>/<camid>/frame_num.npy`` (:172, :206), and a frame number absent from the store is skipped with a
+warning (:209-211).
+"""
+import os
+
+import numpy as np
+import yaml
+
+SKELETON = "v1"    # visualize_result.py's draw_kps; visualize_result_2 sets "v2"
+
+
+def _gpu_renderer(cgroup, height, width, skeleton, mrksize, device):
+    from mqhip.overlay import OverlayRenderer
+    return OverlayRenderer(cgroup, height, width, skeleton=skeleton, mrksize=mrksize, device=device)
+
+
+def proc(data_name, i_cam, config_path, raw_data_dir=None, results_dir_root='./results3D', out_dir='./output',
+         device=0, batch=16, step=1, frame_range=None, skeleton=None, mrksize=3, renderer=None):
+    """visualize_result.py:136-254 for camera ``camera_id[i_cam]`` of ``config_path``.
+
+    ``step`` / ``frame_range=(start, stop)`` select the rows ``range(start, stop, step)`` of kp3d's frame axis
+    (a full camera of the workload is 2.8 GB of frames); ``batch`` output images are rendered per launch, and
+    the source images a batch needs are uploaded once (stores may keep a pool of images shared by many frames).
+    ``renderer``: a factory ``(cgroup, height, width, skeleton, mrksize, device)`` of an object with
+    ``OverlayRenderer.render``'s signature (tests inject the NumPy oracle); the default is the GPU renderer.
+    Returns the written store's directory, or None on the early returns."""
+    from mqhip import io as mqio
+    from mqhip.geometry import CameraGroup
+    skeleton = SKELETON if skeleton is None else skeleton
+    result_dir = os.path.join(results_dir_root, data_name)
+
+    with open(config_path, 'r') as f:
+        cfg = yaml.safe_load(f)
+    ID = cfg['camera_id']
+
+    vid_path = os.path.join(out_dir, data_name + '_{:d}'.format(ID[i_cam]))
+
+    if os.path.exists(os.path.join(vid_path, 'metadata.yaml')):
+        print('already exists:', vid_path)
+        return None
+
+    if os.path.exists(result_dir + '/kp3d_fxdJointLen.pickle'):
+        kp3d_file = result_dir + '/kp3d_fxdJointLen.pickle'
+    elif os.path.exists(result_dir + '/kp3d.pickle'):
+        kp3d_file = result_dir + '/kp3d.pickle'
+    else:
+        print('no kp3d file:', data_name)
+        return None
+
+    print('generating...', vid_path)
+
+    data = mqio.load_array_pickle(kp3d_file)
+    data_name = os.path.basename(os.path.normpath(result_dir))
+    mdata = raw_data_dir + '/' + data_name.split('.')[0] + '.' + str(ID[i_cam])
+    frame_num = np.load(result_dir + '/' + str(ID[i_cam]) + '/frame_num.npy')
+    store = mqio.FrameStore(mdata)
+    store_frames_set = set(int(f) for f in store.get_frame_metadata()['frame_number'])
+
+    X = np.asarray(data['kp3d'], dtype=np.float64)          # (A, F, J, 3)
+    S = np.asarray(data['kp3d_score'], dtype=np.float64)    # (A, F, J)
+    n_animal, n_frame, n_kp, _ = X.shape
+    if len(frame_num) < n_frame:
+        raise IndexError(f'{result_dir}/{ID[i_cam]}/frame_num.npy has {len(frame_num)} rows for {n_frame} frames')
+
+    start, stop = (0, n_frame) if frame_range is None else frame_range
+    rows = []                                               # (i_frame, frame number) of the frames to render
+    for i_frame in range(max(0, int(start)), min(n_frame, int(stop)), max(1, int(step))):
+        fn = int(frame_num[i_frame])
+        if fn not in store_frames_set:
+            print(f'[warning] Skipping frame {fn}: not found in the frame store')
+            continue
+        rows.append((i_frame, fn))
+
+    H, W = (int(v) for v in store.frames.shape[1:3])
+    cgroup = CameraGroup.load(result_dir + '/calibration.toml', device=device).subset_cameras_names([str(ID[i_cam])])
+    draw = (renderer or _gpu_renderer)(cgroup, H, W, skeleton, mrksize, device)
+    writer = mqio.FrameStoreWriter(vid_path, len(rows), H, W, ID[i_cam])
+    batch = max(1, int(batch))
+    for k in range(0, len(rows), batch):
+        part = rows[k:k + batch]
+        idx = np.array([i for i, _ in part])
+        fns = [fn for _, fn in part]
+        pos = [store.index_of(fn) for fn in fns]
+        pool, src_index = np.unique(store.frame_index[pos], return_inverse=True)
+        frames = np.stack([np.asarray(store.frames[int(p)]) for p in pool])      # each source image once
+        out = draw.render(frames, 0, X[:, idx].transpose(1, 0, 2, 3), S[:, idx].transpose(1, 0, 2),
+                          src_index=src_index.astype(np.int32))
+        out = out.cpu().numpy() if hasattr(out, 'cpu') else np.asarray(out)
+        writer.append(out, fns, store.frame_time[pos])
+    writer.close()
+    return vid_path
+
+
+if __name__ == '__main__':
+
+    pass
