@@ -574,6 +574,29 @@ int mq_overlay_render(mq_ctx* ctx, const double* cams, int n_cams, const int32_t
                       int64_t frame_stride, int n_src, const int32_t* src_index, int height, int width,
                       int32_t* prim_i, double* prim_d, uint8_t* out, void* stream);
 
+/* Bundle adjustment of the camera rig on marker traces (multicam_toolbox.py optimize_extrinsic :488-636 and
+ * optimize_all_camera_params :638-824): a Schur-complement Levenberg-Marquardt with Marquardt scaling that
+ * stands in for the reference's least_squares(method='trf', x_scale='jac') call (:611, :776).
+ *   mode       : 0 -- 6 parameters per camera (rvec, tvec), residual (R X + t)[:2] / (R X + t)[2] - undistorted
+ *                point (:566-589); 1 -- 16 per camera in the reference's order rvec, tvec, K00, K01, K02, K11,
+ *                K12, xi, D[4] (:692-694), residual = omnidir projection - pixel (:724-751)
+ *   cam_params : HOST float64 (n_cams, 6 or 16), in / out;  n_cams <= 16
+ *   points3d   : device float64 (n_points, 3), in / out
+ *   obs        : device float64 (n_cams, n_points, 2);  use : device uint8 (n_points, n_cams)
+ *   fix_cam0   : freeze camera 0's six extrinsic parameters (:585-586, :746-747); a camera nobody observes keeps
+ *                its parameters
+ *   ftol       : stop when an accepted step with gain ratio > 1/4 lowers the cost by less than ftol * cost
+ *                (the reference: 1e-5 :611, 1e-3 :639);  xtol: step norm below xtol * (xtol + |x|)
+ *   max_iter   : trial steps (accepted or rejected); 0 only evaluates
+ *   resid      : device float64 (n_points, n_cams, 2) or NULL: residuals at the returned parameters, 0 where unused
+ *   info       : HOST, 8 doubles: initial cost, final cost (1/2 sum r^2), trial steps, stop reason (1 max_iter,
+ *                2 ftol, 3 xtol, 4 damping exhausted), accepted steps, final lambda, linearisations, free camera
+ *                unknowns
+ * Every sum has a fixed order (no floating-point atomics): two calls give the same bits.  Synchronises stream. */
+int mq_bundle_adjust(mq_ctx* ctx, int mode, int n_cams, int n_points, double* cam_params, double* points3d,
+                     const double* obs, const uint8_t* use, int fix_cam0, double ftol, double xtol, int max_iter,
+                     double* resid, double* info, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

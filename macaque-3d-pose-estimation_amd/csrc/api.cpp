@@ -15,6 +15,7 @@
 #include <string>
 #include <vector>
 
+#include "bundle.hpp"
 #include "cmc.hpp"
 #include "geometry.hpp"
 #include "overlay.hpp"
@@ -83,6 +84,7 @@ struct mq_ctx {
   DevBuf assoc_ws;  // step-2 affinity: rays + pairwise distances
   DevBuf det_ws;    // detector post-processing (sort, NMS masks)
   DevBuf dlt_ws;    // mq_triangulate_dlt: undistorted points
+  DevBuf ba_ws;     // mq_bundle_adjust: per-observation blocks, partials, trial points
   mq::SiftWs* sift_ws = nullptr;  // SIFT pyramid + candidates of the stage entry points (mq_sift_*)
 };
 
@@ -239,6 +241,7 @@ int mq_destroy(mq_ctx* ctx) {
   ctx->optim_ws.release();
   ctx->assoc_ws.release();
   ctx->dlt_ws.release();
+  ctx->ba_ws.release();
   ctx->det_ws.release();
   mq::sift_ws_destroy(ctx->sift_ws);
   delete ctx;
@@ -1611,6 +1614,28 @@ int mq_overlay_render(mq_ctx* ctx, const double* cams, int C, const int32_t* cam
   if (rc || n_img == 0) return rc;
   K_TRY(mq::overlay_draw(frames, frame_stride, n_src, src_index, n_img, height, width, A, J, P, mrksize, prim_i,
                          prim_d, out, (hipStream_t)stream));
+  return 0;
+}
+
+// ----------------------------------------------------------------------------- rig bundle adjustment
+int mq_bundle_adjust(mq_ctx* ctx, int mode, int n_cams, int n_points, double* cam_params, double* points3d,
+                     const double* obs, const uint8_t* use, int fix_cam0, double ftol, double xtol, int max_iter,
+                     double* resid, double* info, void* stream) {
+  if (!ctx) return fail("mq_bundle_adjust: null ctx");
+  if (mode != 0 && mode != 1) return fail("mq_bundle_adjust: mode must be 0 (extrinsics) or 1 (all parameters)", -2);
+  if (n_cams < 1 || n_cams > mq::BA_MAXC_API) return fail("mq_bundle_adjust: n_cams must be in [1, 16]", -2);
+  if (n_points < 1 || n_points > (1 << 24)) return fail("mq_bundle_adjust: n_points must be in [1, 2^24]", -2);
+  if (!cam_params || !points3d || !obs || !use || !info) return fail("mq_bundle_adjust: null argument");
+  if (!(ftol >= 0.0) || !(xtol >= 0.0) || max_iter < 0) return fail("mq_bundle_adjust: bad tolerance or max_iter", -2);
+  const int P = mode ? 16 : 6;
+  for (int k = 0; k < n_cams * P; ++k)
+    if (!std::isfinite(cam_params[k])) return fail("mq_bundle_adjust: non-finite camera parameter", -2);
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (ctx->ba_ws.ensure(mq::bundle_workspace_bytes(mode, n_cams, n_points)))
+    return fail("mq_bundle_adjust: out of device memory", -5);
+  const int rc = mq::bundle_adjust(mode, n_cams, n_points, cam_params, points3d, obs, use, fix_cam0, ftol, xtol,
+                                   max_iter, resid, info, ctx->ba_ws.p, (hipStream_t)stream);
+  if (rc != 0) return fail("mq_bundle_adjust: solver failed (" + std::to_string(rc) + ")", rc == -5 ? -5 : -6);
   return 0;
 }
 

@@ -28,6 +28,7 @@ EXPORTED = [
     "mq_cmc_create", "mq_cmc_destroy", "mq_cmc_reset", "mq_cmc_apply",
     "mq_tracklet_traces", "mq_tracklet_id_votes",
     "mq_overlay_primitives", "mq_overlay_render",
+    "mq_bundle_adjust",
 ]
 
 
@@ -117,6 +118,7 @@ _SIGS = {
     "mq_overlay_primitives": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, i32, vp, vp, vp]),
     "mq_overlay_render": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, i32, vp, i64, i32, vp, i32, i32,
                                 vp, vp, vp, vp]),
+    "mq_bundle_adjust": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, i32, f64, f64, i32, vp, vp, vp]),
     "mq_optim_points": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, vp, i32, i32, vp, f64, f64, f64, i32, i32, i32,
                               i32, f64, i32, vp, vp]),
 }
