@@ -153,6 +153,26 @@ int mq_decode_udp(mq_ctx* ctx, const float* heatmaps, int n, int n_joints, int h
                   const float* center, const float* scale, double* kp_img, float* score, int32_t* argmax,
                   float* kp_hm, void* stream);
 
+/* mq_decode_udp keeping up to n_cand (1..4) peaks per (instance, joint) instead of the first argmax only
+ * (the reference's codec, td-hm_ViTPose-huge_8xb64-210e_coco-256x192_sn_macaque.py:4-14, keeps one; the
+ * consumers of several are filter_pose.py:151-186 and cameras.py:639-724).
+ *   kp_img float64 (n, J, n_cand, 2); score float32 (n, J, n_cand); peak int32 (n, J, n_cand) flat heatmap
+ *   index; kp_hm float32 (n, J, n_cand, 2) (may be NULL).  Empty slots hold NaN, 0, -1, NaN.
+ * The rule, on the raw averaged heatmap H of one (instance, joint):
+ *   - pixel p is a peak iff H[p] > min_score and every in-map 8-neighbour q has H[p] > H[q], or
+ *     H[p] == H[q] with flat index p < q (a plateau yields one peak, its lowest index);
+ *   - slots are filled greedily: the highest remaining peak (lowest flat index on ties) whose Chebyshev
+ *     distance to every peak already taken is > min_sep, until n_cand slots are full or no peak is left;
+ *   - slot 0 is mq_decode_udp's result bit for bit in all four outputs (also for max <= 0: loc -1);
+ *   - when the map's maximum is <= max(0, min_score) there are no peaks: slots 1.. stay empty;
+ *   - slot k >= 1 gets the same DARK-UDP step on the same log-blurred map and the same image-space
+ *     mapping; its score is H[peak].
+ * NaN heatmaps: defined for slot 0 only (as mq_decode_udp).  min_sep 3 and min_score 0 are the defaults
+ * of the Python layer. */
+int mq_decode_udp_topk(mq_ctx* ctx, const float* heatmaps, int n, int n_joints, int hm_h, int hm_w,
+                       const float* center, const float* scale, int n_cand, int min_sep, float min_score,
+                       double* kp_img, float* score, int32_t* peak, float* kp_hm, void* stream);
+
 /* crop -> forward(flip) -> decode in one call (inference_topdown batched over boxes of
  * many views).  heatmaps may be NULL. */
 int mq_topdown(mq_vitpose* model, const uint8_t* frames, int64_t frame_stride, int height, int width,
@@ -353,10 +373,21 @@ int mq_triangulate_dlt(mq_ctx* ctx, const double* cams, int n_cams, const double
 int mq_reproj_error(mq_ctx* ctx, const double* cams, int n_cams, const double* p3d, const double* p2d, int n,
                     int mean, double* out, void* stream);
 
-/* CameraGroup.triangulate_ransac (triangulate_possible, n_possible = 1):
+/* CameraGroup.triangulate_ransac (triangulate_possible with n_possible = 1, cameras.py:724-743):
  * p3d (N,3), picked uint8 (C,N), p2d (C,N,2), err (N).  threshold 0.5 in the reference. */
 int mq_triangulate_ransac(mq_ctx* ctx, const double* cams, int n_cams, const double* pts, int n, int min_cams,
                           double threshold, double* p3d, uint8_t* picked, double* p2d, double* err, void* stream);
+
+/* CameraGroup.triangulate_possible (cameras.py:639-724): pts (C, N, P, 2) raw pixels, NaN = absent, P
+ * candidates per camera and point.  Cameras with a non-NaN candidate take part in ascending order, each
+ * with its candidates in ascending index and then "none"; combinations run in itertools.product order
+ * (first camera slowest), skipped when len < min_cams and len != the number of cameras taking part; DLT
+ * on undistorted points, mean reprojection error, strict err < best (best starts at 200), stop at the
+ * first err < threshold.  p3d (N,3), picked uint8 (C,N,P), p2d (C,N,2), err (N).
+ * n_cams <= 16, P <= 4 and (P + 1)^n_cams <= 65,536, else -2. */
+int mq_triangulate_possible(mq_ctx* ctx, const double* cams, int n_cams, const double* pts, int n, int n_possible,
+                            int min_cams, double threshold, double* p3d, uint8_t* picked, double* p2d, double* err,
+                            void* stream);
 
 /* multicam_toolbox.triangulatePoints: und (C,N,2) undistorted, use uint8 (N,C) -> out (N,3). */
 int mq_triangulate_pinv(mq_ctx* ctx, const double* cams, int n_cams, const double* und, const uint8_t* use, int n,
@@ -421,6 +452,16 @@ int mq_match_svt(mq_ctx* ctx, const double* S, const int32_t* n_det, const int32
  * owned by the context.  score_threshold 0.3, n_back 3, offset_threshold 25 in step 4 (n_back 1..3). */
 int mq_viterbi_filter(mq_ctx* ctx, const double* kp, int n_animals, int n_frames, int n_cams, int n_joints,
                       double score_threshold, int n_back, double offset_threshold, double* out, void* stream);
+
+/* filter_pose_viterbi with n_possible candidates per (frame, joint) (filter_pose.py:26-46 remove_dups,
+ * 48-120 viterbi_path, 151-186): kp (A,F,C,J,K,3) [x, y, score], K = n_possible in 1..4 -> out (A,F,C,J,3).
+ * A candidate with score < score_threshold is NaN; candidate k of a frame is dropped when a lower-index
+ * candidate of the frame lies within 5 px (remove_dups); a frame's particles are the surviving candidates
+ * of frames i, i-1, ..., i-n_back+1 (ascending candidate index within a frame, scores times 2^-j), or
+ * the single (-1, -1, 0.001) when none survives.  n_back 1..3.  K = 1 gives mq_viterbi_filter's bits. */
+int mq_viterbi_filter_multi(mq_ctx* ctx, const double* kp, int n_animals, int n_frames, int n_cams, int n_joints,
+                            int n_possible, double score_threshold, int n_back, double offset_threshold,
+                            double* out, void* stream);
 
 /* Global multi-head self-attention of the ViT encoder (mmpretrain MultiheadAttention, qkv_bias,
  * scale 1/sqrt(head_dim)) -- the building block inside mq_vitpose_forward.

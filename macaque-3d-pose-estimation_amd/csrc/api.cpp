@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "bundle.hpp"
+#include "candidates.hpp"
 #include "cmc.hpp"
 #include "geometry.hpp"
 #include "overlay.hpp"
@@ -738,6 +739,23 @@ int mq_decode_udp(mq_ctx* ctx, const float* heatmaps, int n, int J, int hm_h, in
   return 0;
 }
 
+int mq_decode_udp_topk(mq_ctx* ctx, const float* heatmaps, int n, int J, int hm_h, int hm_w, const float* center,
+                       const float* scale, int n_cand, int min_sep, float min_score, double* kp_img, float* score,
+                       int32_t* peak, float* kp_hm, void* stream) {
+  if (!ctx) return fail("mq_decode_udp_topk: null ctx");
+  if (n < 0 || J <= 0 || hm_h <= 0 || hm_w <= 0) return fail("mq_decode_udp_topk: bad sizes");
+  if (n_cand < 1 || n_cand > 4) return fail("mq_decode_udp_topk: n_cand must be in [1, 4]", -2);
+  if (min_sep < 0) return fail("mq_decode_udp_topk: min_sep must be >= 0", -2);
+  if (n == 0) return 0;
+  if (!heatmaps || !center || !scale || !kp_img || !score || !peak) return fail("mq_decode_udp_topk: null buffer");
+  if ((size_t)(hm_h * hm_w + (hm_h + 10) * hm_w) * 4 > 64 * 1024) return fail("mq_decode_udp_topk: heatmap too large");
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (ctx->decode_work.ensure((size_t)n * J * hm_h * hm_w * 4)) return fail("decode workspace alloc failed", -5);
+  K_TRY(mq::udp_decode_topk(heatmaps, n, J, hm_h, hm_w, center, scale, 192, 256, n_cand, min_sep, min_score,
+                            ctx->decode_work.as<float>(), kp_img, score, peak, kp_hm, (hipStream_t)stream));
+  return 0;
+}
+
 int mq_topdown(mq_vitpose* m, const uint8_t* frames, int64_t frame_stride, int height, int width, const float* boxes,
                const int32_t* box_frame, int n, int flip_test, double* kp_img, float* score, int32_t* argmax,
                float* heatmaps, void* stream) {
@@ -1172,6 +1190,22 @@ int mq_triangulate_ransac(mq_ctx* ctx, const double* cams, int C, const double* 
   return 0;
 }
 
+int mq_triangulate_possible(mq_ctx* ctx, const double* cams, int C, const double* pts, int n, int n_possible,
+                            int min_cams, double threshold, double* p3d, uint8_t* picked, double* p2d, double* err,
+                            void* stream) {
+  int rc = check_geo(ctx, cams, C, n);
+  if (rc) return rc;
+  if (n_possible < 1 || n_possible > 4) return fail("mq_triangulate_possible: n_possible must be in [1, 4]", -2);
+  int64_t combos = 1;
+  for (int c = 0; c < C; ++c) combos *= n_possible + 1;
+  if (combos > 65536) return fail("mq_triangulate_possible: (n_possible + 1)^n_cams must be <= 65536", -2);
+  if (n == 0) return 0;
+  if (!pts || !p3d || !picked || !p2d || !err) return fail("mq_triangulate_possible: null argument");
+  K_TRY(mq::triangulate_possible(cams, C, pts, n, n_possible, min_cams, threshold, p3d, picked, p2d, err,
+                                 (hipStream_t)stream));
+  return 0;
+}
+
 int mq_triangulate_pinv(mq_ctx* ctx, const double* cams, int C, const double* und, const uint8_t* use, int n,
                         double* out, void* stream) {
   int rc = check_geo(ctx, cams, C, n);
@@ -1258,6 +1292,22 @@ int mq_viterbi_filter(mq_ctx* ctx, const double* kp, int A, int F, int C, int J,
   if (ctx->scratch.ensure(mq::viterbi_scratch_bytes(A, F, C, J, n_back))) return fail("viterbi scratch alloc failed", -5);
   K_TRY(mq::viterbi_filter(kp, A, F, C, J, score_threshold, n_back, offset_threshold, ctx->scratch.p, out,
                            (hipStream_t)stream));
+  return 0;
+}
+
+int mq_viterbi_filter_multi(mq_ctx* ctx, const double* kp, int A, int F, int C, int J, int K, double score_threshold,
+                            int n_back, double offset_threshold, double* out, void* stream) {
+  if (!ctx || !kp || !out) return fail("mq_viterbi_filter_multi: null argument");
+  if (A < 0 || F < 0 || C < 0 || J < 0) return fail("mq_viterbi_filter_multi: negative size", -2);
+  if (K < 1 || K > 4) return fail("mq_viterbi_filter_multi: n_possible must be in [1, 4]", -2);
+  if (n_back < 1 || n_back > 3) return fail("mq_viterbi_filter_multi: n_back must be in [1, 3]", -2);
+  if ((int64_t)A * F * C * J == 0) return 0;
+  if ((int64_t)A * C * J > (int64_t)1 << 30) return fail("mq_viterbi_filter_multi: too many chains", -2);
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (ctx->scratch.ensure(mq::viterbi_multi_scratch_bytes(A, F, C, J, K, n_back)))
+    return fail("viterbi scratch alloc failed", -5);
+  K_TRY(mq::viterbi_filter_multi(kp, A, F, C, J, K, score_threshold, n_back, offset_threshold, ctx->scratch.p, out,
+                                 (hipStream_t)stream));
   return 0;
 }
 

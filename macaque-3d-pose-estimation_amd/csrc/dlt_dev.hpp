@@ -1,5 +1,6 @@
-// Device helpers shared by the float64 geometry kernels (geometry.hip) and the tracklet lift
-// (tracklet.hip): the camera row accessor, the one-sided Jacobi SVD and the mvpose pinv DLT solve.
+// Device helpers shared by the float64 geometry kernels (geometry.hip), the tracklet lift (tracklet.hip)
+// and the candidate kernels (candidates.hip): the camera row accessor, the one-sided Jacobi SVD, the
+// mvpose pinv DLT solve and the homogeneous DLT.
 // Translation units including this are built with -ffp-contract=off (the numpy oracle's rounding order).
 #pragma once
 #include "common.hpp"
@@ -116,6 +117,46 @@ __device__ __forceinline__ void pinv_dlt_solve(const double* cams, int C, const 
   out[0] = -X[0];
   out[1] = -X[1];
   out[2] = -X[2];
+}
+
+// Homogeneous DLT (cameras.py:20-32) over the cameras flagged in `use`.
+template <int MAXC>
+__device__ __forceinline__ void dlt_point(const double* cams, int C, const double* ux, const double* uy,
+                                          unsigned use, double out[3]) {
+  double a[4][2 * MAXC];
+#pragma unroll
+  for (int c = 0; c < MAXC; ++c) {
+    const bool on = (c < C) && ((use >> c) & 1u);
+    if (on) {
+      const CamParams& cp = cam_at(cams, c);
+      const double P0[4] = {cp.R[0], cp.R[1], cp.R[2], cp.t[0]};
+      const double P1[4] = {cp.R[3], cp.R[4], cp.R[5], cp.t[1]};
+      const double P2[4] = {cp.R[6], cp.R[7], cp.R[8], cp.t[2]};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        a[k][2 * c] = ux[c] * P2[k] - P0[k];
+        a[k][2 * c + 1] = uy[c] * P2[k] - P1[k];
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        a[k][2 * c] = 0.0;
+        a[k][2 * c + 1] = 0.0;
+      }
+    }
+  }
+  double V[4][4], sig[4];
+  jacobi_svd<2 * MAXC, 4>(a, V, sig);
+  int jmin = 0;
+#pragma unroll
+  for (int j = 1; j < 4; ++j)
+    if (sig[j] < sig[jmin]) jmin = j;
+  double v[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) v[k] = V[jmin][k];
+  out[0] = v[0] / v[3];
+  out[1] = v[1] / v[3];
+  out[2] = v[2] / v[3];
 }
 
 }  // namespace mq

@@ -4,49 +4,9 @@
 #include "camera.hpp"
 #include "geometry.hpp"
 #include "dlt_dev.hpp"
+#include "viterbi_dev.hpp"
 
 namespace mq {
-
-// Homogeneous DLT (cameras.py:20-32) over the cameras flagged in `use`.
-template <int MAXC>
-__device__ __forceinline__ void dlt_point(const double* cams, int C, const double* ux, const double* uy,
-                                          unsigned use, double out[3]) {
-  double a[4][2 * MAXC];
-#pragma unroll
-  for (int c = 0; c < MAXC; ++c) {
-    const bool on = (c < C) && ((use >> c) & 1u);
-    if (on) {
-      const CamParams& cp = cam_at(cams, c);
-      const double P0[4] = {cp.R[0], cp.R[1], cp.R[2], cp.t[0]};
-      const double P1[4] = {cp.R[3], cp.R[4], cp.R[5], cp.t[1]};
-      const double P2[4] = {cp.R[6], cp.R[7], cp.R[8], cp.t[2]};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        a[k][2 * c] = ux[c] * P2[k] - P0[k];
-        a[k][2 * c + 1] = uy[c] * P2[k] - P1[k];
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        a[k][2 * c] = 0.0;
-        a[k][2 * c + 1] = 0.0;
-      }
-    }
-  }
-  double V[4][4], sig[4];
-  jacobi_svd<2 * MAXC, 4>(a, V, sig);
-  int jmin = 0;
-#pragma unroll
-  for (int j = 1; j < 4; ++j)
-    if (sig[j] < sig[jmin]) jmin = j;
-  double v[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) v[k] = V[jmin][k];
-  out[0] = v[0] / v[3];
-  out[1] = v[1] / v[3];
-  out[2] = v[2] / v[3];
-}
-
 
 // ------------------------------------------------------------------ step-2 geometry affinity
 // geometry_affinity2 (step2_crossviewmatching.py:373-432) batched over B frames of up to M detections
@@ -435,31 +395,6 @@ __global__ void pinv_dlt_kernel(const double* __restrict__ cams, int C, const do
 }
 
 // ------------------------------------------------------------------ Viterbi (filter_pose.py:48-186)
-// scipy log_ndtr (Faddeeva form): x < -1: log(erfcx(-t)/2) - t^2, else log1p(-erfc(t)/2), t = x/sqrt(2),
-// erfc(t) = exp(-t^2) erfcx(t) (t >= 0) or 2 - exp(-t^2) erfcx(-t).
-__device__ __forceinline__ double log_ndtr_d(double x) {
-  const double t = x * 0.70710678118654752440;
-  if (x < -1.0) return log(erfcx(-t) / 2) - t * t;
-  const double e = (t < 0) ? (2. - exp(-t * t) * erfcx(-t)) : exp(-t * t) * erfcx(t);
-  return log1p(-e / 2);
-}
-
-// log(Phi((d+2)/s) - Phi((d-2)/s)) evaluated as scipy's logsumexp(b=[1,-1]) does, clamped at -100.
-__device__ __forceinline__ double trans_logprob(double d, double thres) {
-  const double hi = log_ndtr_d((d + 2) / thres);
-  const double lo = log_ndtr_d((d - 2) / thres);
-  double r;
-  if (hi > lo) {
-    r = log1p(-exp(lo - hi)) + hi;
-  } else if (hi == lo) {
-    r = -INFINITY;
-  } else {
-    r = NAN;
-  }
-  if (r < -100) r = -100;
-  return r;
-}
-
 // The Viterbi filter in two launches (filter_pose.py:48-120, chain = (animal, camera, joint)):
 //  1. viterbi_trans_kernel, one thread per (chain, frame i, particle q of frame i, particle p of
 //     frame i-1): the transition log-probability log(Phi((d+2)/s) - Phi((d-2)/s)) -- the fp64

@@ -457,6 +457,34 @@ class CameraGroup:
         return (p3d.cpu().numpy(), picked.cpu().numpy().astype(bool).reshape(C, n, 1), p2d.cpu().numpy(),
                 err.cpu().numpy())
 
+    def triangulate_possible(self, points, undistort=True, min_cams=2, progress=False, threshold=0.5):
+        """CxNxPx2 (NaN = absent) -> (p3d Nx3, picked CxNxP, p2ds CxNx2, errors N) (cameras.py:639-724).
+
+        C <= 16, P <= 4 and (P + 1)^C <= 65,536 combinations per point, else ValueError."""
+        assert points.shape[0] == len(self.cameras), \
+            "Invalid points shape, first dim should be equal to" \
+            " number of cameras ({}), but shape is {}".format(len(self.cameras), points.shape)
+        if not undistort:
+            raise NotImplementedError("triangulate_possible(undistort=False) is not on the reference's path")
+        C, n, P, _ = points.shape
+        if not (1 <= C <= 16 and 1 <= P <= 4 and (P + 1) ** C <= 65536):
+            raise ValueError(f"triangulate_possible: {C} cameras x {P} candidates is outside C <= 16, P <= 4, "
+                             f"(P + 1)^C <= 65536")
+        ctx = self._ctx()
+        dev = self._dev()
+        p3d = torch.empty((n, 3), dtype=torch.float64, device=dev)
+        picked = torch.empty((C, n, P), dtype=torch.uint8, device=dev)
+        p2d = torch.empty((C, n, 2), dtype=torch.float64, device=dev)
+        err = torch.empty((n,), dtype=torch.float64, device=dev)
+        pts_d = self._to_dev(points)
+        rc = ctx.lib.mq_triangulate_possible(ctx.handle, _lib.ptr(self.cams_tensor()), C, _lib.ptr(pts_d), n, P,
+                                             int(min_cams), float(threshold), _lib.ptr(p3d), _lib.ptr(picked),
+                                             _lib.ptr(p2d), _lib.ptr(err), _lib.stream_ptr(dev))
+        if rc == -2:
+            raise ValueError("mq_triangulate_possible: " + ctx.lib.mq_last_error().decode())
+        _lib.check(rc, "mq_triangulate_possible")
+        return p3d.cpu().numpy(), picked.cpu().numpy().astype(bool), p2d.cpu().numpy(), err.cpu().numpy()
+
     def reprojection_error(self, p3ds, p2ds, mean=False):
         """cameras.py:746-783."""
         one_point = False
@@ -537,11 +565,24 @@ def triangulate_pinv(cams: CameraGroup, und, frame_use):
 
 
 def viterbi_filter(kp2d, score_threshold=0.3, n_back=3, offset_threshold=25, device: int = 0):
-    """Batched filter_pose_viterbi over kp2d (A,F,C,J,3) -> filtered (A,F,C,J,3) (step4:142-167)."""
+    """Batched filter_pose_viterbi over kp2d (A,F,C,J,3) -> filtered (A,F,C,J,3) (step4:142-167).
+
+    A 6-D kp2d (A,F,C,J,K,3) carries K = n_possible candidates (1..4) per (frame, joint) and goes to
+    mq_viterbi_filter_multi (filter_pose.py:26-120); the output is (A,F,C,J,3) either way."""
     kp = np.ascontiguousarray(kp2d, dtype=np.float64)
-    A, F, C, J, _ = kp.shape
     ctx = _lib.Context.get(device)
     dev = torch.device("cuda", device)
+    if kp.ndim == 6:
+        A, F, C, J, K, _ = kp.shape
+        if not 1 <= K <= 4:
+            raise ValueError(f"viterbi_filter: n_possible must be in [1, 4], got {K}")
+        src = torch.from_numpy(kp).to(dev)
+        out = torch.empty((A, F, C, J, 3), dtype=torch.float64, device=dev)
+        _lib.check(ctx.lib.mq_viterbi_filter_multi(ctx.handle, _lib.ptr(src), A, F, C, J, K, float(score_threshold),
+                                                   int(n_back), float(offset_threshold), _lib.ptr(out),
+                                                   _lib.stream_ptr(dev)), "mq_viterbi_filter_multi")
+        return out.cpu().numpy()
+    A, F, C, J, _ = kp.shape
     src = torch.from_numpy(kp).to(dev)
     out = torch.empty_like(src)
     _lib.check(ctx.lib.mq_viterbi_filter(ctx.handle, _lib.ptr(src), A, F, C, J, float(score_threshold), int(n_back),

@@ -78,7 +78,13 @@ class VitPoseHip:
                                                _lib.stream_ptr(self.dev)), "mq_vitpose_forward")
         return out
 
-    def decode(self, heatmaps: torch.Tensor, center: torch.Tensor, scale: torch.Tensor):
+    def decode(self, heatmaps: torch.Tensor, center: torch.Tensor, scale: torch.Tensor, n_candidates=None,
+               min_sep: int = 3, min_score: float = 0.0):
+        """``n_candidates=None``: mq_decode_udp, one location per joint.  An int K in 1..4: the top-K
+        peaks (``decode_heatmaps_topk``), every output with a candidate axis after the joint axis."""
+        if n_candidates is not None:
+            return decode_heatmaps_topk(heatmaps, center, scale, n_candidates, min_sep=min_sep,
+                                        min_score=min_score, device=self.device)
         n, J, hh, ww = heatmaps.shape
         heatmaps = heatmaps.contiguous()
         kp = torch.empty((n, J, 2), device=self.dev, dtype=torch.float64)
@@ -92,11 +98,11 @@ class VitPoseHip:
                    "mq_decode_udp")
         return kp, score, am, kp_hm
 
-    def topdown(self, frames, boxes, box_frame, flip_test=True):
-        """inference_topdown over every box of every view in one batch."""
+    def topdown(self, frames, boxes, box_frame, flip_test=True, n_candidates=None):
+        """inference_topdown over every box of every view in one batch (``n_candidates``: see decode)."""
         crops, center, scale = self.crop(frames, boxes, box_frame)
         hm = self.forward(crops, flip_test)
-        kp, score, am, _ = self.decode(hm, center, scale)
+        kp, score, am, _ = self.decode(hm, center, scale, n_candidates=n_candidates)
         return kp, score, am
 
 
@@ -115,6 +121,35 @@ def decode_heatmaps(heatmaps: torch.Tensor, center: torch.Tensor, scale: torch.T
                                      _lib.ptr(score), _lib.ptr(am), _lib.ptr(kp_hm), _lib.stream_ptr(dev)),
                "mq_decode_udp")
     return kp, score, am, kp_hm
+
+
+def decode_heatmaps_topk(heatmaps: torch.Tensor, center: torch.Tensor, scale: torch.Tensor, n_candidates: int,
+                         min_sep: int = 3, min_score: float = 0.0, device: int = 0):
+    """mq_decode_udp_topk: up to ``n_candidates`` (1..4) peaks per (instance, joint).
+
+    Returns kp (n,J,K,2) f64 image pixels, score (n,J,K) f32, peak (n,J,K) i32 flat heatmap index and
+    kp_hm (n,J,K,2) f32.  A pixel is a peak when it is > ``min_score`` and beats its 8 neighbours (ties:
+    lowest flat index); slots are filled by descending height with a Chebyshev distance > ``min_sep``
+    to every peak already taken.  Slot 0 is ``decode_heatmaps``' result bit for bit; empty slots hold
+    NaN, 0, -1, NaN."""
+    K = int(n_candidates)
+    if not 1 <= K <= 4:
+        raise ValueError(f"n_candidates must be in [1, 4], got {n_candidates}")
+    if int(min_sep) < 0:
+        raise ValueError(f"min_sep must be >= 0, got {min_sep}")
+    ctx = _lib.Context.get(device)
+    dev = torch.device("cuda", device)
+    n, J, hh, ww = heatmaps.shape
+    kp = torch.empty((n, J, K, 2), device=dev, dtype=torch.float64)
+    score = torch.empty((n, J, K), device=dev, dtype=torch.float32)
+    peak = torch.empty((n, J, K), device=dev, dtype=torch.int32)
+    kp_hm = torch.empty((n, J, K, 2), device=dev, dtype=torch.float32)
+    heatmaps, center, scale = heatmaps.contiguous(), center.contiguous(), scale.contiguous()
+    _lib.check(ctx.lib.mq_decode_udp_topk(ctx.handle, _lib.ptr(heatmaps), n, J, hh, ww,
+                                          _lib.ptr(center), _lib.ptr(scale), K, int(min_sep), float(min_score),
+                                          _lib.ptr(kp), _lib.ptr(score), _lib.ptr(peak), _lib.ptr(kp_hm),
+                                          _lib.stream_ptr(dev)), "mq_decode_udp_topk")
+    return kp, score, peak, kp_hm
 
 
 def crop_boxes(frames: torch.Tensor, boxes: torch.Tensor, box_frame: torch.Tensor, device: int = 0):

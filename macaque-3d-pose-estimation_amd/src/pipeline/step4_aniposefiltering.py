@@ -132,7 +132,8 @@ def write_calibration(config_path, result_dir, cam_ids):
 
 
 def filter_2d(kp2d, filter_config=FILTER_CONFIG, device: int = 0):
-    """step4:140-170: kp2d (A,F,C,J,3) -> kp2d_f (F,J,A,3,C) (filtered points + Viterbi scores)."""
+    """step4:140-170: kp2d (A,F,C,J,3) -> kp2d_f (F,J,A,3,C) (filtered points + Viterbi scores).
+    kp2d may carry K = 1..4 candidates per (frame, joint) as (A,F,C,J,K,3); the output shape is the same."""
     fc = filter_config['filter']
     out = viterbi_filter(kp2d, score_threshold=fc['score_threshold'], n_back=fc['n_back'],
                          offset_threshold=fc['offset_threshold'], device=device)
@@ -223,7 +224,8 @@ def reconstruct_3d(kp2d_f, cgroup, config, bodyparts=BODYPARTS, joint_len_median
 def proc(data_name, results_dir_root, config_path, n_kp, redo=False, device: int = 0, verbose=False, kp2d=None,
          world=1, rank=0, group=None):
     """step4_aniposefiltering.proc (step4:89).  ``kp2d``: step 3's (A, F, C, J, 3) array in memory (as
-    written to kp2d.pickle) instead of reading the file back.
+    written to kp2d.pickle) instead of reading the file back, or (A, F, C, J, K, 3) with K = 1..4 candidates per
+    (frame, joint) for the Viterbi filter to choose from (everything after the filter is unchanged).
 
     ``world`` > 1 (every rank calls this with the same gathered ``kp2d``): rank r filters and lifts the
     individuals a with a % world == r, one object all-gather brings their results to rank 0, which writes the
