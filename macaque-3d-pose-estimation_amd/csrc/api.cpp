@@ -725,15 +725,28 @@ int mq_crop_udp(mq_ctx* ctx, const uint8_t* frames, int64_t frame_stride, int he
   return 0;
 }
 
-int mq_decode_udp(mq_ctx* ctx, const float* heatmaps, int n, int J, int hm_h, int hm_w, const float* center,
-                  const float* scale, double* kp_img, float* score, int32_t* argmax, float* kp_hm, void* stream) {
-  if (!ctx) return fail("mq_decode_udp: null ctx");
-  if (n < 0 || J <= 0 || hm_h <= 0 || hm_w <= 0) return fail("mq_decode_udp: bad sizes");
-  if (n == 0) return 0;
-  if (!heatmaps || !center || !scale || !kp_img || !score || !argmax) return fail("mq_decode_udp: null buffer");
-  if ((size_t)(hm_h * hm_w + (hm_h + 10) * hm_w) * 4 > 64 * 1024) return fail("mq_decode_udp: heatmap too large");
+// The checks and the workspace the two decode entry points share.  0: go on; 1: nothing to do (n == 0);
+// < 0: error.  `name` prefixes the messages; n_cand and min_sep are checked between the sizes and the buffers.
+static int decode_prepare(mq_ctx* ctx, const char* name, bool buffers_ok, int n, int J, int hm_h, int hm_w,
+                          int n_cand, int min_sep) {
+  const std::string who = name;
+  if (!ctx) return fail(who + ": null ctx");
+  if (n < 0 || J <= 0 || hm_h <= 0 || hm_w <= 0) return fail(who + ": bad sizes");
+  if (n_cand < 1 || n_cand > 4) return fail(who + ": n_cand must be in [1, 4]", -2);
+  if (min_sep < 0) return fail(who + ": min_sep must be >= 0", -2);
+  if (n == 0) return 1;
+  if (!buffers_ok) return fail(who + ": null buffer");
+  if ((size_t)(hm_h * hm_w + (hm_h + 10) * hm_w) * 4 > 64 * 1024) return fail(who + ": heatmap too large");
   HIP_TRY(hipSetDevice(ctx->device));
   if (ctx->decode_work.ensure((size_t)n * J * hm_h * hm_w * 4)) return fail("decode workspace alloc failed", -5);
+  return 0;
+}
+
+int mq_decode_udp(mq_ctx* ctx, const float* heatmaps, int n, int J, int hm_h, int hm_w, const float* center,
+                  const float* scale, double* kp_img, float* score, int32_t* argmax, float* kp_hm, void* stream) {
+  const int rc = decode_prepare(ctx, "mq_decode_udp", heatmaps && center && scale && kp_img && score && argmax, n, J,
+                                hm_h, hm_w, 1, 0);
+  if (rc) return rc < 0 ? rc : 0;
   K_TRY(mq::udp_decode(heatmaps, n, J, hm_h, hm_w, center, scale, 192, 256, ctx->decode_work.as<float>(), kp_img,
                        score, argmax, kp_hm, (hipStream_t)stream));
   return 0;
@@ -742,15 +755,9 @@ int mq_decode_udp(mq_ctx* ctx, const float* heatmaps, int n, int J, int hm_h, in
 int mq_decode_udp_topk(mq_ctx* ctx, const float* heatmaps, int n, int J, int hm_h, int hm_w, const float* center,
                        const float* scale, int n_cand, int min_sep, float min_score, double* kp_img, float* score,
                        int32_t* peak, float* kp_hm, void* stream) {
-  if (!ctx) return fail("mq_decode_udp_topk: null ctx");
-  if (n < 0 || J <= 0 || hm_h <= 0 || hm_w <= 0) return fail("mq_decode_udp_topk: bad sizes");
-  if (n_cand < 1 || n_cand > 4) return fail("mq_decode_udp_topk: n_cand must be in [1, 4]", -2);
-  if (min_sep < 0) return fail("mq_decode_udp_topk: min_sep must be >= 0", -2);
-  if (n == 0) return 0;
-  if (!heatmaps || !center || !scale || !kp_img || !score || !peak) return fail("mq_decode_udp_topk: null buffer");
-  if ((size_t)(hm_h * hm_w + (hm_h + 10) * hm_w) * 4 > 64 * 1024) return fail("mq_decode_udp_topk: heatmap too large");
-  HIP_TRY(hipSetDevice(ctx->device));
-  if (ctx->decode_work.ensure((size_t)n * J * hm_h * hm_w * 4)) return fail("decode workspace alloc failed", -5);
+  const int rc = decode_prepare(ctx, "mq_decode_udp_topk", heatmaps && center && scale && kp_img && score && peak, n,
+                                J, hm_h, hm_w, n_cand, min_sep);
+  if (rc) return rc < 0 ? rc : 0;
   K_TRY(mq::udp_decode_topk(heatmaps, n, J, hm_h, hm_w, center, scale, 192, 256, n_cand, min_sep, min_score,
                             ctx->decode_work.as<float>(), kp_img, score, peak, kp_hm, (hipStream_t)stream));
   return 0;

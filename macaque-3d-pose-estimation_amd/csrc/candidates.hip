@@ -1,10 +1,9 @@
-// More than one candidate per (instance, joint): the top-K heatmap peaks (mq_decode_udp_topk) and
-// the two anipose consumers that choose among candidates, the n_possible > 1 Viterbi filter
-// (mq_viterbi_filter_multi, filter_pose.py:26-120,151-186) and CameraGroup.triangulate_possible
-// (mq_triangulate_possible, cameras.py:639-724).
-// Compiled with -ffp-contract=off: every expression rounds like the numpy / scipy oracle and like
-// the single-candidate kernels (imgproc.hip, geometry.hip), whose results slot 0 / K = 1 / P = 1
-// reproduce bit for bit.
+// The two anipose consumers that choose among more than one candidate per (instance, joint): the
+// n_possible > 1 Viterbi filter (mq_viterbi_filter_multi, filter_pose.py:26-120,151-186) and
+// CameraGroup.triangulate_possible (mq_triangulate_possible, cameras.py:639-724).  The candidates come from
+// the top-K heatmap decode (mq_decode_udp_topk, imgproc.hip).
+// Compiled with -ffp-contract=off: every expression rounds like the numpy / scipy oracle and like the
+// single-candidate kernels (geometry.hip), whose results K = 1 / P = 1 reproduce bit for bit.
 #include "common.hpp"
 #include "camera.hpp"
 #include "candidates.hpp"
@@ -12,309 +11,6 @@
 #include "viterbi_dev.hpp"
 
 namespace mq {
-
-// ------------------------------------------------------------------ top-K peaks + DARK-UDP decode
-// The 11-tap Gaussian of decode_blur_kernel (imgproc.hip kGauss11; a __constant__ table cannot be
-// shared across translation units): cv2.getGaussianKernel(11, sigma 0 -> 2.0) in float64, rounded
-// to float32.  A CPU test pins both tables against oracle/decode.py:gaussian_kernel_1d.
-__constant__ float kGauss11Cand[11] = {
-    0.00881222914904356f, 0.027143577113747597f, 0.06511405855417252f, 0.12164907157421112f,
-    0.17699836194515228f, 0.2005654126405716f,   0.17699836194515228f, 0.12164907157421112f,
-    0.06511405855417252f, 0.027143577113747597f, 0.00881222914904356f};
-
-constexpr int CAND_MAX = 4;
-
-// Block argmax of (value, flat index) pairs: highest value, lowest index on ties; index 0x7fffffff
-// = "nothing".  The result is left in red_v[0] / red_i[0]; the caller synchronises before reuse.
-__device__ __forceinline__ void block_best(float bv, int bi, float* red_v, int* red_i) {
-  red_v[threadIdx.x] = bv;
-  red_i[threadIdx.x] = bi;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) {
-      const float v2 = red_v[threadIdx.x + o];
-      const int i2 = red_i[threadIdx.x + o];
-      const float v1 = red_v[threadIdx.x];
-      const int i1 = red_i[threadIdx.x];
-      const bool none1 = i1 == 0x7fffffff, none2 = i2 == 0x7fffffff;
-      if (!none2 && (none1 || v2 > v1 || (v2 == v1 && i2 < i1))) {
-        red_v[threadIdx.x] = v2;
-        red_i[threadIdx.x] = i2;
-      }
-    }
-    __syncthreads();
-  }
-}
-
-// Stage 1, one block per (instance, joint): decode_blur_kernel's first argmax, blur, rescale, clip and
-// log with the same operations in the same order, plus the peak rule on the raw map before the blur
-// overwrites it: peaks are flagged in parallel (into the not yet used row buffer), then n_cand - 1
-// rounds of block argmax take the highest peak farther than min_sep (Chebyshev) from every peak taken.
-__global__ __launch_bounds__(256) void topk_blur_kernel(const float* __restrict__ avg, int HH, int WW, int n_cand,
-                                                        int min_sep, float min_score, float* __restrict__ work,
-                                                        int32_t* __restrict__ peak, float* __restrict__ score) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int nk = blockIdx.x;
-  const int plane = HH * WW;
-  const int PR = HH + 10;  // padded rows
-  float* hmap = sm;          // HH*WW
-  float* rows = sm + plane;  // PR*WW (peak flags first, then the row-filtered padded rows)
-  __shared__ float red_v[256];
-  __shared__ int red_i[256];
-  __shared__ int tk_i[CAND_MAX];
-  __shared__ float tk_v[CAND_MAX];
-  const float* src = avg + (int64_t)nk * plane;
-  float bv = -INFINITY;
-  int bi = 0x7fffffff;
-  for (int i = threadIdx.x; i < plane; i += blockDim.x) {
-    const float v = src[i];
-    hmap[i] = v;
-    if (v > bv || (v == bv && i < bi) || (v != v && bv == bv)) {  // NaN counts as max (np.argmax)
-      bv = v;
-      bi = i;
-    }
-  }
-  red_v[threadIdx.x] = bv;
-  red_i[threadIdx.x] = bi;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) {
-      const float v2 = red_v[threadIdx.x + o];
-      const int i2 = red_i[threadIdx.x + o];
-      const float v1 = red_v[threadIdx.x];
-      const int i1 = red_i[threadIdx.x];
-      const bool n1 = v1 != v1, n2 = v2 != v2;
-      bool take2;
-      if (n1 || n2)
-        take2 = n2 && (!n1 || i2 < i1);
-      else
-        take2 = (v2 > v1) || (v2 == v1 && i2 < i1);
-      if (take2) {
-        red_v[threadIdx.x] = v2;
-        red_i[threadIdx.x] = i2;
-      }
-    }
-    __syncthreads();
-  }
-  const float origin_max = red_v[0];
-  const int origin_arg = red_i[0];
-  __syncthreads();  // red_* are reused below
-  // ---- slots 1..: the peak rule on the raw map
-  const bool any_peak = origin_max > fmaxf(0.f, min_score);  // false for a NaN maximum
-  if (threadIdx.x == 0) {
-    tk_i[0] = origin_arg;
-    tk_v[0] = origin_max;
-    for (int k = 1; k < CAND_MAX; ++k) {
-      tk_i[k] = -1;
-      tk_v[k] = 0.f;
-    }
-  }
-  if (n_cand > 1 && any_peak) {
-    for (int i = threadIdx.x; i < plane; i += blockDim.x) {
-      const float v = hmap[i];
-      const int y = i / WW, x = i % WW;
-      bool pk = v > min_score;
-      for (int dy = -1; dy <= 1 && pk; ++dy) {
-        const int yy = y + dy;
-        if (yy < 0 || yy >= HH) continue;
-        for (int dx = -1; dx <= 1; ++dx) {
-          const int xx = x + dx;
-          if ((dx == 0 && dy == 0) || xx < 0 || xx >= WW) continue;
-          const int q = yy * WW + xx;
-          const float hq = hmap[q];
-          if (!(v > hq || (v == hq && i < q))) pk = false;
-        }
-      }
-      rows[i] = pk ? 1.f : 0.f;
-    }
-    __syncthreads();
-    for (int k = 1; k < n_cand; ++k) {
-      float cv = -INFINITY;
-      int ci = 0x7fffffff;
-      for (int i = threadIdx.x; i < plane; i += blockDim.x) {
-        if (rows[i] == 0.f) continue;
-        const int y = i / WW, x = i % WW;
-        bool far = true;
-        for (int t = 0; t < k; ++t) {
-          const int ty = tk_i[t] / WW, tx = tk_i[t] % WW;
-          const int ax = x > tx ? x - tx : tx - x, ay = y > ty ? y - ty : ty - y;
-          if ((ax > ay ? ax : ay) <= min_sep) far = false;
-        }
-        if (!far) continue;
-        const float v = hmap[i];
-        if (ci == 0x7fffffff || v > cv) {  // ascending i: the first of equal values stays
-          cv = v;
-          ci = i;
-        }
-      }
-      block_best(cv, ci, red_v, red_i);
-      const int got = red_i[0];
-      const float gotv = red_v[0];
-      __syncthreads();
-      if (got == 0x7fffffff) break;  // no peak left (uniform across the block)
-      if (threadIdx.x == 0) {
-        tk_i[k] = got;
-        tk_v[k] = gotv;
-      }
-      __syncthreads();
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < n_cand) {
-    peak[(int64_t)nk * n_cand + threadIdx.x] = tk_i[threadIdx.x];
-    score[(int64_t)nk * n_cand + threadIdx.x] = tk_v[threadIdx.x];
-  }
-  __syncthreads();  // the peak flags in rows are dead from here
-  // ---- decode_blur_kernel's blur: row pass over the padded map: rows[r][x] = sum_t g[t] * dr[r][x + t]
-  for (int i = threadIdx.x; i < PR * WW; i += blockDim.x) {
-    const int r = i / WW, x = i % WW;
-    const int yy = r - 5;
-    float acc;
-    if (yy < 0 || yy >= HH) {
-      acc = 0.f;
-    } else {
-      const float* hr = hmap + yy * WW;
-      int c = x - 5;
-      acc = kGauss11Cand[0] * ((c >= 0 && c < WW) ? hr[c] : 0.f);
-      for (int t = 1; t < 11; ++t) {
-        c = x + t - 5;
-        acc = acc + kGauss11Cand[t] * ((c >= 0 && c < WW) ? hr[c] : 0.f);
-      }
-    }
-    rows[i] = acc;
-  }
-  __syncthreads();
-  // column pass -> blurred (stored back into hmap), track its max
-  float lmax = -INFINITY;
-  for (int i = threadIdx.x; i < plane; i += blockDim.x) {
-    const int y = i / WW, x = i % WW;
-    float acc = kGauss11Cand[0] * rows[y * WW + x];
-    for (int t = 1; t < 11; ++t) acc = acc + kGauss11Cand[t] * rows[(y + t) * WW + x];
-    hmap[i] = acc;
-    lmax = fmaxf(lmax, acc);
-  }
-  __syncthreads();
-  red_v[threadIdx.x] = lmax;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) red_v[threadIdx.x] = fmaxf(red_v[threadIdx.x], red_v[threadIdx.x + o]);
-    __syncthreads();
-  }
-  const float ratio = origin_max / red_v[0];
-  float* dst = work + (int64_t)nk * plane;
-  for (int i = threadIdx.x; i < plane; i += blockDim.x) {
-    float v = hmap[i] * ratio;
-    v = fminf(fmaxf(v, 0.001f), 50.0f);
-    dst[i] = logf(v);
-  }
-}
-
-// imgproc.hip's padded_at: element of numpy's flattened edge-padded (J, H+2, W+2) log map with Python
-// negative-index wrap-around (slot 0 of a joint whose max <= 0 reads through it, loc = -1).
-__device__ __forceinline__ float cand_padded_at(const float* work_inst, int K, int HH, int WW, long idx) {
-  const long per = (long)(HH + 2) * (WW + 2);
-  const long total = per * K;
-  if (idx < 0) idx += total;
-  const int k = (int)(idx / per);
-  const int rem = (int)(idx % per);
-  int pr = rem / (WW + 2) - 1, pc = rem % (WW + 2) - 1;
-  pr = pr < 0 ? 0 : (pr >= HH ? HH - 1 : pr);
-  pc = pc < 0 ? 0 : (pc >= WW ? WW - 1 : pc);
-  return work_inst[((long)k * HH + pr) * WW + pc];
-}
-
-// Stage 2, one thread per (instance, joint, slot): decode_refine_kernel's DARK-UDP Newton step and
-// image-space mapping, same arithmetic, started from the slot's peak.  Slot 0 keeps the loc = -1 rule
-// for max <= 0; a slot >= 1 is a peak inside the map, so its reads stay inside its own joint's map.
-__global__ void topk_refine_kernel(const float* __restrict__ work, const int32_t* __restrict__ peak,
-                                   const float* __restrict__ score, int N, int K, int n_cand, int HH, int WW,
-                                   const float* __restrict__ center, const float* __restrict__ scale, int in_w,
-                                   int in_h, double* __restrict__ kp_img, float* __restrict__ kp_hm) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= N * K * n_cand) return;
-  const int slot = t % n_cand;
-  const int i = t / n_cand;
-  const int n = i / K, k = i % K;
-  if (slot > 0 && (peak[t] < 0 || peak[t] >= HH * WW)) {  // empty slot
-    kp_img[2 * t] = NAN;
-    kp_img[2 * t + 1] = NAN;
-    if (kp_hm) {
-      kp_hm[2 * t] = NAN;
-      kp_hm[2 * t + 1] = NAN;
-    }
-    return;
-  }
-  const float* wi = work + (long)n * K * HH * WW;
-  float lx, ly;
-  if (slot == 0 && score[t] <= 0.f) {
-    lx = -1.f;
-    ly = -1.f;
-  } else {
-    lx = (float)(peak[t] % WW);
-    ly = (float)(peak[t] / WW);
-  }
-  const int W2 = WW + 2;
-  const float fidx = lx + 1.f + (ly + 1.f) * (float)W2;
-  const long index = (long)fidx + (long)W2 * (HH + 2) * k;
-  const float i_ = cand_padded_at(wi, K, HH, WW, index);
-  const float ix1 = cand_padded_at(wi, K, HH, WW, index + 1);
-  const float iy1 = cand_padded_at(wi, K, HH, WW, index + W2);
-  const float ix1y1 = cand_padded_at(wi, K, HH, WW, index + W2 + 1);
-  const float ix1_y1_ = cand_padded_at(wi, K, HH, WW, index - W2 - 1);
-  const float ix1_ = cand_padded_at(wi, K, HH, WW, index - 1);
-  const float iy1_ = cand_padded_at(wi, K, HH, WW, index - W2);
-  const float dx = 0.5f * (ix1 - ix1_);
-  const float dy = 0.5f * (iy1 - iy1_);
-  const float dxx = ix1 - 2.f * i_ + ix1_;
-  const float dxy = 0.5f * (ix1y1 - ix1 - iy1 + i_ + i_ - ix1_ - iy1_ + ix1_y1_);
-  const float dyy = iy1 - 2.f * i_ + iy1_;
-  const double eps = 1.1920928955078125e-07;
-  // inv([[a b][c d]]) by LU with partial pivoting (LAPACK getrf/getrs order)
-  double a = (double)dxx + eps, b = (double)dxy + 0.0, c = (double)dxy + 0.0, d = (double)dyy + eps;
-  bool swap = fabs(c) > fabs(a);
-  double p = swap ? c : a, q = swap ? d : b, r = swap ? a : c, s = swap ? b : d;
-  const double l = r * (1.0 / p);
-  const double u22 = s - l * q;
-  double inv[2][2];
-  for (int j = 0; j < 2; ++j) {
-    double b1 = (j == 0) ? (swap ? 0.0 : 1.0) : (swap ? 1.0 : 0.0);
-    double b2 = (j == 0) ? (swap ? 1.0 : 0.0) : (swap ? 0.0 : 1.0);
-    b2 = b2 - l * b1;
-    b2 = b2 / u22;
-    b1 = b1 - b2 * q;
-    b1 = b1 / p;
-    inv[0][j] = b1;
-    inv[1][j] = b2;
-  }
-  const double stx = inv[0][0] * (double)dx + inv[0][1] * (double)dy;
-  const double sty = inv[1][0] * (double)dx + inv[1][1] * (double)dy;
-  const float kx = (float)((double)lx - stx);
-  const float ky = (float)((double)ly - sty);
-  if (kp_hm) {
-    kp_hm[2 * t] = kx;
-    kp_hm[2 * t + 1] = ky;
-  }
-  const double ix = (double)kx / (double)(WW - 1) * (double)in_w;
-  const double iy = (double)ky / (double)(HH - 1) * (double)in_h;
-  const float s0 = scale[2 * n], s1 = scale[2 * n + 1];
-  const float h0 = 0.5f * s0, h1 = 0.5f * s1;
-  kp_img[2 * t] = ix / (double)in_w * (double)s0 + (double)center[2 * n] - (double)h0;
-  kp_img[2 * t + 1] = iy / (double)in_h * (double)s1 + (double)center[2 * n + 1] - (double)h1;
-}
-
-int udp_decode_topk(const float* avg, int n, int joints, int h, int w, const float* center, const float* scale,
-                    int in_w, int in_h, int n_cand, int min_sep, float min_score, float* work, double* kp_img,
-                    float* score, int32_t* peak, float* kp_hm, hipStream_t s) {
-  if (n <= 0) return 0;
-  if (n_cand < 1 || n_cand > CAND_MAX) return -2;
-  const size_t lds = (size_t)(h * w + (h + 10) * w) * sizeof(float);
-  hipLaunchKernelGGL(topk_blur_kernel, dim3(n * joints), dim3(256), lds, s, avg, h, w, n_cand, min_sep, min_score,
-                     work, peak, score);
-  const int tot = n * joints * n_cand;
-  hipLaunchKernelGGL(topk_refine_kernel, dim3((tot + 127) / 128), dim3(128), 0, s, work, peak, score, n, joints,
-                     n_cand, h, w, center, scale, in_w, in_h, kp_img, kp_hm);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
 
 // ------------------------------------------------------------------ Viterbi, n_possible > 1
 // filter_pose.py:26-46 (remove_dups), 48-120 (viterbi_path), 151-186 (filter_pose_viterbi) for
@@ -504,12 +200,78 @@ int viterbi_filter_multi(const double* kp, int A, int F, int C, int J, int K, do
 }
 
 // ------------------------------------------------------------------ triangulate_possible (cameras.py:639-724)
-// ransac_kernel for P candidates per camera.  One wave per point; the cameras with a non-NaN candidate
-// take part, each with its candidates in ascending k and then "none", so a combination is a mixed-radix
-// number whose slowest digit is the first camera (itertools.product order).  Lanes evaluate 64
-// combinations at a time; the first chunk holding an error < threshold ends the search at its first
-// such combination (the serial early exit), otherwise the first strict minimum below 200 wins.
-// Raw and undistorted candidates sit in LDS; a lane gathers its combination into registers.
+// and, with one candidate per camera, triangulate_ransac (cameras.py:726-743).
+
+// DLT over the cameras of `use` whose undistortion succeeded (ux[c] not NaN) into p, then the mean
+// reprojection error of p over the cameras of `use` (CameraGroup.reprojection_error(mean=True): NaN norms
+// dropped, fewer than two -> NaN).  raw(c, u, v) gives the raw pixel of camera c.
+template <int MAXC, class Raw>
+__device__ __forceinline__ double reproj_mean_error(const double* cams, int C, unsigned use,
+                                                    const double (&ux)[MAXC], const double (&uy)[MAXC], Raw raw,
+                                                    double (&p)[3]) {
+  unsigned ok = 0;
+#pragma unroll
+  for (int c = 0; c < MAXC; ++c)
+    if (((use >> c) & 1u) && !(ux[c] != ux[c])) ok |= 1u << c;
+  p[0] = p[1] = p[2] = NAN;
+  if (__popc(ok) >= 2) dlt_point<MAXC>(cams, C, ux, uy, ok, p);
+  double sum = 0.0, cnt = 0.0;
+  for (int c = 0; c < C; ++c) {
+    if (!((use >> c) & 1u)) continue;
+    double u, v, ru, rv;
+    cam_project(cam_at(cams, c), p[0], p[1], p[2], u, v);
+    raw(c, ru, rv);
+    const double ex = ru - u, ey = rv - v;
+    const double nr = sqrt(ex * ex + ey * ey);
+    if (!(nr != nr)) {
+      sum = sum + nr;
+      cnt = cnt + 1.0;
+    }
+  }
+  return (cnt < 1.5) ? NAN : sum / cnt;
+}
+
+// The search of one wave over subsets 0..nsub-1 in the serial (itertools.product) order: lane l takes
+// err_of(base + l) (NaN = subset not tried), 64 subsets at a time.  The first chunk holding an error
+// < threshold ends the search at its first such subset, which reproduces the serial early exit exactly;
+// otherwise the first strict minimum below 200 wins, or -1.  The result is uniform across the wave.
+template <class ErrOf>
+__device__ __forceinline__ int first_hit_or_min(int nsub, double threshold, ErrOf err_of) {
+  const int lane = threadIdx.x;
+  double best_err = 200.0;
+  int best_s = 0x7fffffff;
+  for (int base = 0; base < nsub; base += 64) {
+    const int s = base + lane;
+    double err = NAN;
+    if (s < nsub) err = err_of(s);
+    // first subset (smallest s) in this chunk with err < threshold
+    const bool hit = err < threshold;
+    const unsigned long long hits = __ballot(hit);
+    if (hits) return base + __ffsll((long long)hits) - 1;
+    // running strict minimum, ties keep the earlier subset
+    double e = (err < 200.0) ? err : INFINITY;
+    int es = (err < 200.0) ? s : 0x7fffffff;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const double e2 = __shfl_xor(e, o, 64);
+      const int s2 = __shfl_xor(es, o, 64);
+      if (e2 < e || (e2 == e && s2 < es)) {
+        e = e2;
+        es = s2;
+      }
+    }
+    if (es != 0x7fffffff && (e < best_err || (e == best_err && es < best_s))) {
+      best_err = e;
+      best_s = es;
+    }
+  }
+  return best_s != 0x7fffffff ? best_s : -1;
+}
+
+// One wave per point; the cameras with a non-NaN candidate take part, each with its candidates in
+// ascending k and then "none", so a combination is a mixed-radix number whose slowest digit is the first
+// camera (itertools.product order), searched by first_hit_or_min.  Raw and undistorted candidates sit in
+// LDS; a lane gathers its combination into registers.
 template <int MAXC>
 __global__ __launch_bounds__(64) void possible_kernel(const double* __restrict__ cams, int C,
                                                       const double* __restrict__ pts, int N, int P, int min_cams,
@@ -576,81 +338,32 @@ __global__ __launch_bounds__(64) void possible_kernel(const double* __restrict__
       }
     }
   };
-  // DLT over the used cameras whose undistortion succeeded, then the mean reprojection error over the
-  // used cameras (CameraGroup.reprojection_error(mean=True): NaN norms dropped, fewer than two -> NaN)
-  auto evaluate = [&](unsigned use, unsigned sel, const double (&ux)[MAXC], const double (&uy)[MAXC],
-                      double (&p)[3]) -> double {
-    unsigned ok = 0;
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c)
-      if (((use >> c) & 1u) && !(ux[c] != ux[c])) ok |= 1u << c;
-    p[0] = p[1] = p[2] = NAN;
-    if (__popc(ok) >= 2) dlt_point<MAXC>(cams, C, ux, uy, ok, p);
-    double sum = 0.0, cnt = 0.0;
-    for (int c = 0; c < C; ++c) {
-      if (!((use >> c) & 1u)) continue;
+  // raw pixel of camera c in a combination whose candidates are sel
+  const auto raw_of = [&](unsigned sel) {
+    return [sel](int c, double& u, double& v) {
       const int k = (sel >> (2 * c)) & 3u;
-      double u, v;
-      cam_project(cam_at(cams, c), p[0], p[1], p[2], u, v);
-      const double ex = s_raw[c * CAND_MAX + k][0] - u, ey = s_raw[c * CAND_MAX + k][1] - v;
-      const double nr = sqrt(ex * ex + ey * ey);
-      if (!(nr != nr)) {
-        sum = sum + nr;
-        cnt = cnt + 1.0;
-      }
-    }
-    return (cnt < 1.5) ? NAN : sum / cnt;
+      u = s_raw[c * CAND_MAX + k][0];
+      v = s_raw[c * CAND_MAX + k][1];
+    };
   };
-  int chosen = -1;
-  double best_err = 200.0;
-  int best_s = 0x7fffffff;
   double ux[MAXC], uy[MAXC];
-  if (m >= 2) {
-    for (int base = 0; base < nsub; base += 64) {
-      const int s = base + lane;
-      double err = NAN;
-      if (s < nsub) {
-        unsigned use, sel;
-        gather(s, use, sel, ux, uy);
-        const int k = __popc(use);
-        if (!(k < min_cams && k != m) && k >= 2) {
-          double p[3];
-          err = evaluate(use, sel, ux, uy, p);
-        }
-      }
-      // first combination (smallest s) in this chunk with err < threshold
-      const bool hit = err < threshold;
-      const unsigned long long hits = __ballot(hit);
-      if (hits) {
-        chosen = base + __ffsll((long long)hits) - 1;
-        break;
-      }
-      // running strict minimum, ties keep the earlier combination
-      double e = (err < 200.0) ? err : INFINITY;
-      int es = (err < 200.0) ? s : 0x7fffffff;
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const double e2 = __shfl_xor(e, o, 64);
-        const int s2 = __shfl_xor(es, o, 64);
-        if (e2 < e || (e2 == e && s2 < es)) {
-          e = e2;
-          es = s2;
-        }
-      }
-      if (es != 0x7fffffff && (e < best_err || (e == best_err && es < best_s))) {
-        best_err = e;
-        best_s = es;
-      }
-    }
-    if (chosen < 0 && best_s != 0x7fffffff) chosen = best_s;
-  }
+  int chosen = -1;
+  if (m >= 2)
+    chosen = first_hit_or_min(nsub, threshold, [&](int s) -> double {
+      unsigned use, sel;
+      gather(s, use, sel, ux, uy);
+      const int k = __popc(use);
+      if ((k < min_cams && k != m) || k < 2) return NAN;
+      double p[3];
+      return reproj_mean_error<MAXC>(cams, C, use, ux, uy, raw_of(sel), p);
+    });
   if (lane != 0) return;
   double p[3] = {NAN, NAN, NAN};
   double err = 0.0;
   unsigned use = 0, sel = 0;
   if (chosen >= 0) {
     gather(chosen, use, sel, ux, uy);
-    err = evaluate(use, sel, ux, uy, p);
+    err = reproj_mean_error<MAXC>(cams, C, use, ux, uy, raw_of(sel), p);
   }
   out_p3d[3 * (size_t)n] = p[0];
   out_p3d[3 * (size_t)n + 1] = p[1];
@@ -681,6 +394,13 @@ int triangulate_possible(const double* cams, int C, const double* pts, int N, in
     hipLaunchKernelGGL(possible_kernel<16>, dim3(N), dim3(64), 0, s, cams, C, pts, N, P, min_cams, threshold, p3d,
                        picked, p2d, err);
   return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// CameraGroup.triangulate_ransac is triangulate_possible with n_possible = 1: the same subsets in the same
+// order, and picked [C][N][1] is [C][N].
+int triangulate_ransac(const double* cams, int C, const double* pts, int N, int min_cams, double threshold,
+                       double* p3d, uint8_t* picked, double* p2d, double* err, hipStream_t s) {
+  return triangulate_possible(cams, C, pts, N, 1, min_cams, threshold, p3d, picked, p2d, err, s);
 }
 
 }  // namespace mq

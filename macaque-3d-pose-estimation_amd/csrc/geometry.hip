@@ -243,133 +243,6 @@ __global__ void reproj_kernel(const double* __restrict__ cams, int C, const doub
   if (mean) out[n] = (cnt < 1.5) ? NAN : sum / cnt;
 }
 
-// triangulate_ransac -> triangulate_possible (cameras.py:639-743), n_possible = 1.
-// One wave per point; lanes walk the itertools.product order (bit m-1-i of the
-// subset index = "camera position i dropped") 64 subsets at a time and stop at
-// the first chunk holding an error < threshold, which reproduces the serial
-// early exit exactly; otherwise the first strict minimum below 200 wins.
-template <int MAXC>
-__global__ __launch_bounds__(64) void ransac_kernel(const double* __restrict__ cams, int C,
-                                                    const double* __restrict__ pts, int N, int min_cams,
-                                                    double threshold, double* __restrict__ out_p3d,
-                                                    uint8_t* __restrict__ out_picked, double* __restrict__ out_p2d,
-                                                    double* __restrict__ out_err) {
-  const int n = blockIdx.x;
-  const int lane = threadIdx.x;
-  if (n >= N) return;
-  double raw_u[MAXC], raw_v[MAXC], ux[MAXC], uy[MAXC];
-  int pos2cam[MAXC];
-  int m = 0;
-  unsigned und_ok = 0;
-#pragma unroll
-  for (int c = 0; c < MAXC; ++c) {
-    raw_u[c] = raw_v[c] = ux[c] = uy[c] = 0;
-    if (c < C) {
-      const size_t o = 2 * ((size_t)c * N + n);
-      raw_u[c] = pts[o];
-      raw_v[c] = pts[o + 1];
-      if (!(raw_u[c] != raw_u[c])) {
-        cam_undistort(cam_at(cams, c), raw_u[c], raw_v[c], ux[c], uy[c]);
-        if (!(ux[c] != ux[c])) und_ok |= 1u << c;
-        pos2cam[m] = c;
-        ++m;
-      }
-    }
-  }
-  const int nsub = 1 << m;
-  int chosen = -1;
-  double best_err = 200.0;
-  int best_s = 0x7fffffff;
-  if (m >= 2) {
-    for (int base = 0; base < nsub; base += 64) {
-      const int s = base + lane;
-      double err = NAN;
-      if (s < nsub) {
-        unsigned use = 0;
-        int k = 0;
-        for (int i = 0; i < m; ++i)
-          if (!((s >> (m - 1 - i)) & 1)) {
-            use |= 1u << pos2cam[i];
-            ++k;
-          }
-        if (!(k < min_cams && k != m) && k >= 2) {
-          double p[3] = {NAN, NAN, NAN};
-          if (__popc(use & und_ok) >= 2) dlt_point<MAXC>(cams, C, ux, uy, use & und_ok, p);
-          double sum = 0.0, cnt = 0.0;
-          for (int c = 0; c < C; ++c) {
-            if (!((use >> c) & 1u)) continue;
-            double u, v;
-            cam_project(cam_at(cams, c), p[0], p[1], p[2], u, v);
-            const double ex = raw_u[c] - u, ey = raw_v[c] - v;
-            const double nr = sqrt(ex * ex + ey * ey);
-            if (!(nr != nr)) {
-              sum = sum + nr;
-              cnt = cnt + 1.0;
-            }
-          }
-          err = (cnt < 1.5) ? NAN : sum / cnt;
-        }
-      }
-      // first subset (smallest s) in this chunk with err < threshold
-      const bool hit = err < threshold;
-      const unsigned long long hits = __ballot(hit);
-      if (hits) {
-        chosen = base + __ffsll((long long)hits) - 1;
-        break;
-      }
-      // running strict minimum, ties keep the earlier subset
-      double e = (err < 200.0) ? err : INFINITY;
-      int es = (err < 200.0) ? s : 0x7fffffff;
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const double e2 = __shfl_xor(e, o, 64);
-        const int s2 = __shfl_xor(es, o, 64);
-        if (e2 < e || (e2 == e && s2 < es)) {
-          e = e2;
-          es = s2;
-        }
-      }
-      if (es != 0x7fffffff && (e < best_err || (e == best_err && es < best_s))) {
-        best_err = e;
-        best_s = es;
-      }
-    }
-    if (chosen < 0 && best_s != 0x7fffffff) chosen = best_s;
-  }
-  if (lane != 0) return;
-  double p[3] = {NAN, NAN, NAN};
-  double err = 0.0;
-  unsigned use = 0;
-  if (chosen >= 0) {
-    for (int i = 0; i < m; ++i)
-      if (!((chosen >> (m - 1 - i)) & 1)) use |= 1u << pos2cam[i];
-    if (__popc(use & und_ok) >= 2) dlt_point<MAXC>(cams, C, ux, uy, use & und_ok, p);
-    double sum = 0.0, cnt = 0.0;
-    for (int c = 0; c < C; ++c) {
-      if (!((use >> c) & 1u)) continue;
-      double u, v;
-      cam_project(cam_at(cams, c), p[0], p[1], p[2], u, v);
-      const double ex = raw_u[c] - u, ey = raw_v[c] - v;
-      const double nr = sqrt(ex * ex + ey * ey);
-      if (!(nr != nr)) {
-        sum = sum + nr;
-        cnt = cnt + 1.0;
-      }
-    }
-    err = (cnt < 1.5) ? NAN : sum / cnt;
-  }
-  out_p3d[3 * n] = p[0];
-  out_p3d[3 * n + 1] = p[1];
-  out_p3d[3 * n + 2] = p[2];
-  out_err[n] = err;
-  for (int c = 0; c < C; ++c) {
-    const bool on = (use >> c) & 1u;
-    out_picked[(size_t)c * N + n] = on ? 1 : 0;
-    out_p2d[2 * ((size_t)c * N + n)] = on ? raw_u[c] : NAN;
-    out_p2d[2 * ((size_t)c * N + n) + 1] = on ? raw_v[c] : NAN;
-  }
-}
-
 // mvpose inhomogeneous DLT (multicam_toolbox.py:433-486): X = pinv(A[:, :3]) A[:, 3], P = -X.
 template <int MAXC>
 __global__ void pinv_dlt_kernel(const double* __restrict__ cams, int C, const double* __restrict__ und,
@@ -595,20 +468,6 @@ int reprojection_error(const double* cams, int C, const double* p3d, const doubl
                        hipStream_t s) {
   if (N <= 0) return 0;
   hipLaunchKernelGGL(reproj_kernel, dim3((N + 127) / 128), dim3(128), 0, s, cams, C, p3d, p2d, N, mean, out);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int triangulate_ransac(const double* cams, int C, const double* pts, int N, int min_cams, double threshold,
-                       double* p3d, uint8_t* picked, double* p2d, double* err, hipStream_t s) {
-  if (N <= 0) return 0;
-  if (C <= 8)
-    hipLaunchKernelGGL(ransac_kernel<8>, dim3(N), dim3(64), 0, s, cams, C, pts, N, min_cams, threshold, p3d, picked,
-                       p2d, err);
-  else if (C <= 16)
-    hipLaunchKernelGGL(ransac_kernel<16>, dim3(N), dim3(64), 0, s, cams, C, pts, N, min_cams, threshold, p3d, picked,
-                       p2d, err);
-  else
-    return -2;
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -9,8 +9,6 @@ int omnidir_project(const double* cams, int C, const double* p3d, double* out, i
 int triangulate_dlt(const double* cams, int C, const double* pts, int N, int undistort, double* out, hipStream_t s);
 int reprojection_error(const double* cams, int C, const double* p3d, const double* p2d, int N, int mean, double* out,
                        hipStream_t s);
-int triangulate_ransac(const double* cams, int C, const double* pts, int N, int min_cams, double threshold,
-                       double* p3d, uint8_t* picked, double* p2d, double* err, hipStream_t s);
 int triangulate_pinv(const double* cams, int C, const double* und, const uint8_t* use, int N, double* out,
                      hipStream_t s);
 int geometry_affinity(const double* cams, int C, const double* pts, const int32_t* cam_of_det, int B, int M, int J,

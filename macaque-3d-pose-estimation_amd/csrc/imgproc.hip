@@ -2,6 +2,7 @@
 // floating-point step here follows the operation order of the restated reference
 // (oracle/crop.py, oracle/decode.py) so results are bit-reproducible against it.
 #include "common.hpp"
+#include "candidates.hpp"
 #include "kernels.hpp"
 
 namespace mq {
@@ -143,6 +144,9 @@ int flip_average(const float* hm_all, float* avg, int n, int joints, int h, int 
 }
 
 // ------------------------------------------------------------------ UDP / DARK-UDP decode
+// mq_decode_udp (the first argmax per joint) and mq_decode_udp_topk (up to CAND_MAX peaks per joint) run
+// the same two stages; slot 0 of the top-K decode is the single-candidate result bit for bit.
+//
 // The 11-tap Gaussian of cv2.getGaussianKernel(11, sigma 0 -> 2.0), computed in
 // float64 and rounded to float32 (oracle/decode.py:gaussian_kernel_1d; a CPU
 // test pins this table against it).
@@ -151,17 +155,117 @@ __constant__ float kGauss11[11] = {
     0.17699836194515228f, 0.2005654126405716f,   0.17699836194515228f, 0.12164907157421112f,
     0.06511405855417252f, 0.027143577113747597f, 0.00881222914904356f};
 
-// Stage 1: one block per (instance, joint): first argmax, separable blur of the
-// 5-px zero-padded map, rescale to the original max, clip [1e-3, 50], log.
-__global__ __launch_bounds__(256) void decode_blur_kernel(const float* __restrict__ avg, int K, int HH, int WW,
-                                                          float* __restrict__ work, int32_t* __restrict__ argmax,
-                                                          float* __restrict__ score) {
+// Block argmax of (value, flat index) pairs: highest value, lowest index on ties; index 0x7fffffff
+// = "nothing".  The result is left in red_v[0] / red_i[0]; the caller synchronises before reuse.
+__device__ __forceinline__ void block_best(float bv, int bi, float* red_v, int* red_i) {
+  red_v[threadIdx.x] = bv;
+  red_i[threadIdx.x] = bi;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (threadIdx.x < o) {
+      const float v2 = red_v[threadIdx.x + o];
+      const int i2 = red_i[threadIdx.x + o];
+      const float v1 = red_v[threadIdx.x];
+      const int i1 = red_i[threadIdx.x];
+      const bool none1 = i1 == 0x7fffffff, none2 = i2 == 0x7fffffff;
+      if (!none2 && (none1 || v2 > v1 || (v2 == v1 && i2 < i1))) {
+        red_v[threadIdx.x] = v2;
+        red_i[threadIdx.x] = i2;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// The peak rule of the top-K decode on the raw map (before the blur overwrites it).  Slot 0 is the first
+// argmax; peaks are flagged in parallel (into the not yet used row buffer), then n_cand - 1 rounds of
+// block argmax take the highest peak farther than min_sep (Chebyshev) from every peak taken.
+__device__ __forceinline__ void topk_peaks(const float* hmap, float* flags, float* red_v, int* red_i, int HH, int WW,
+                                           float origin_max, int origin_arg, int n_cand, int min_sep,
+                                           float min_score, int32_t* __restrict__ peak, float* __restrict__ score) {
+  __shared__ int tk_i[CAND_MAX];
+  __shared__ float tk_v[CAND_MAX];
+  const int plane = HH * WW;
+  const bool any_peak = origin_max > fmaxf(0.f, min_score);  // false for a NaN maximum
+  if (threadIdx.x == 0) {
+    tk_i[0] = origin_arg;
+    tk_v[0] = origin_max;
+    for (int k = 1; k < CAND_MAX; ++k) {
+      tk_i[k] = -1;
+      tk_v[k] = 0.f;
+    }
+  }
+  if (n_cand > 1 && any_peak) {
+    for (int i = threadIdx.x; i < plane; i += blockDim.x) {
+      const float v = hmap[i];
+      const int y = i / WW, x = i % WW;
+      bool pk = v > min_score;
+      for (int dy = -1; dy <= 1 && pk; ++dy) {
+        const int yy = y + dy;
+        if (yy < 0 || yy >= HH) continue;
+        for (int dx = -1; dx <= 1; ++dx) {
+          const int xx = x + dx;
+          if ((dx == 0 && dy == 0) || xx < 0 || xx >= WW) continue;
+          const int q = yy * WW + xx;
+          const float hq = hmap[q];
+          if (!(v > hq || (v == hq && i < q))) pk = false;
+        }
+      }
+      flags[i] = pk ? 1.f : 0.f;
+    }
+    __syncthreads();
+    for (int k = 1; k < n_cand; ++k) {
+      float cv = -INFINITY;
+      int ci = 0x7fffffff;
+      for (int i = threadIdx.x; i < plane; i += blockDim.x) {
+        if (flags[i] == 0.f) continue;
+        const int y = i / WW, x = i % WW;
+        bool far = true;
+        for (int t = 0; t < k; ++t) {
+          const int ty = tk_i[t] / WW, tx = tk_i[t] % WW;
+          const int ax = x > tx ? x - tx : tx - x, ay = y > ty ? y - ty : ty - y;
+          if ((ax > ay ? ax : ay) <= min_sep) far = false;
+        }
+        if (!far) continue;
+        const float v = hmap[i];
+        if (ci == 0x7fffffff || v > cv) {  // ascending i: the first of equal values stays
+          cv = v;
+          ci = i;
+        }
+      }
+      block_best(cv, ci, red_v, red_i);
+      const int got = red_i[0];
+      const float gotv = red_v[0];
+      __syncthreads();
+      if (got == 0x7fffffff) break;  // no peak left (uniform across the block)
+      if (threadIdx.x == 0) {
+        tk_i[k] = got;
+        tk_v[k] = gotv;
+      }
+      __syncthreads();
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < n_cand) {
+    peak[threadIdx.x] = tk_i[threadIdx.x];
+    score[threadIdx.x] = tk_v[threadIdx.x];
+  }
+  __syncthreads();  // the peak flags are dead from here
+}
+
+// Stage 1: one block per (instance, joint): first argmax (and, TOPK, the peak rule), separable blur of
+// the 5-px zero-padded map, rescale to the original max, clip [1e-3, 50], log.  peak / score hold n_cand
+// entries per block, 1 when not TOPK (whose instance carries none of the peak rule's code or LDS).
+template <bool TOPK>
+__device__ __forceinline__ void decode_blur_body(const float* __restrict__ avg, int HH, int WW, int n_cand,
+                                                 int min_sep, float min_score, float* __restrict__ work,
+                                                 int32_t* __restrict__ peak, float* __restrict__ score) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int nk = blockIdx.x;
   const int plane = HH * WW;
   const int PR = HH + 10;  // padded rows
   float* hmap = sm;                 // HH*WW
-  float* rows = sm + plane;         // PR*WW (row-filtered padded rows)
+  float* rows = sm + plane;         // PR*WW (TOPK: peak flags first; then the row-filtered padded rows)
   __shared__ float red_v[256];
   __shared__ int red_i[256];
   const float* src = avg + (int64_t)nk * plane;
@@ -198,8 +302,13 @@ __global__ __launch_bounds__(256) void decode_blur_kernel(const float* __restric
     __syncthreads();
   }
   const float origin_max = red_v[0];
-  if (threadIdx.x == 0) {
-    argmax[nk] = red_i[0];
+  if constexpr (TOPK) {
+    const int origin_arg = red_i[0];
+    __syncthreads();  // red_* are reused by the peak rule
+    topk_peaks(hmap, rows, red_v, red_i, HH, WW, origin_max, origin_arg, n_cand, min_sep, min_score,
+               peak + (int64_t)nk * n_cand, score + (int64_t)nk * n_cand);
+  } else if (threadIdx.x == 0) {
+    peak[nk] = red_i[0];
     score[nk] = origin_max;
   }
   // row pass over the padded map: rows[r][x] = sum_t g[t] * dr[r][x + t]
@@ -247,6 +356,18 @@ __global__ __launch_bounds__(256) void decode_blur_kernel(const float* __restric
   }
 }
 
+__global__ __launch_bounds__(256) void decode_blur_kernel(const float* __restrict__ avg, int HH, int WW,
+                                                          float* __restrict__ work, int32_t* __restrict__ argmax,
+                                                          float* __restrict__ score) {
+  decode_blur_body<false>(avg, HH, WW, 1, 0, 0.f, work, argmax, score);
+}
+
+__global__ __launch_bounds__(256) void topk_blur_kernel(const float* __restrict__ avg, int HH, int WW, int n_cand,
+                                                        int min_sep, float min_score, float* __restrict__ work,
+                                                        int32_t* __restrict__ peak, float* __restrict__ score) {
+  decode_blur_body<true>(avg, HH, WW, n_cand, min_sep, min_score, work, peak, score);
+}
+
 // Element of numpy's flattened edge-padded (K, H+2, W+2) log map with Python
 // negative-index wrap-around (refine_keypoints_dark_udp reads through it for
 // joints whose max <= 0, loc = -1).
@@ -262,23 +383,38 @@ __device__ __forceinline__ float padded_at(const float* work_inst, int K, int HH
   return work_inst[((long)k * HH + pr) * WW + pc];
 }
 
-// Stage 2: one thread per (instance, joint): DARK-UDP Newton step (float32
-// derivatives, float64 Hessian inverse), heatmap -> input -> image space.
-__global__ void decode_refine_kernel(const float* __restrict__ work, const int32_t* __restrict__ argmax,
-                                     const float* __restrict__ score, int N, int K, int HH, int WW,
+// Stage 2: one thread per (instance, joint, slot): DARK-UDP Newton step (float32 derivatives, float64
+// Hessian inverse) started from the slot's peak, heatmap -> input -> image space.  Slot 0 keeps the
+// loc = -1 rule for max <= 0; a slot >= 1 is a peak inside the map, so its reads stay inside its own
+// joint's map, and an empty one gives NaN.  The single-candidate instance (not TOPK) has one slot.
+template <bool TOPK>
+__global__ void decode_refine_kernel(const float* __restrict__ work, const int32_t* __restrict__ peak,
+                                     const float* __restrict__ score, int N, int K, int n_cand_arg, int HH, int WW,
                                      const float* __restrict__ center, const float* __restrict__ scale, int in_w,
                                      int in_h, double* __restrict__ kp_img, float* __restrict__ kp_hm) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N * K) return;
+  const int n_cand = TOPK ? n_cand_arg : 1;
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= N * K * n_cand) return;
+  const int slot = t % n_cand;
+  const int i = t / n_cand;
   const int n = i / K, k = i % K;
+  if (slot > 0 && (peak[t] < 0 || peak[t] >= HH * WW)) {  // empty slot
+    kp_img[2 * t] = NAN;
+    kp_img[2 * t + 1] = NAN;
+    if (kp_hm) {
+      kp_hm[2 * t] = NAN;
+      kp_hm[2 * t + 1] = NAN;
+    }
+    return;
+  }
   const float* wi = work + (long)n * K * HH * WW;
   float lx, ly;
-  if (score[i] <= 0.f) {
+  if (slot == 0 && score[t] <= 0.f) {
     lx = -1.f;
     ly = -1.f;
   } else {
-    lx = (float)(argmax[i] % WW);
-    ly = (float)(argmax[i] / WW);
+    lx = (float)(peak[t] % WW);
+    ly = (float)(peak[t] / WW);
   }
   const int W2 = WW + 2;
   const float fidx = lx + 1.f + (ly + 1.f) * (float)W2;
@@ -318,25 +454,39 @@ __global__ void decode_refine_kernel(const float* __restrict__ work, const int32
   const float kx = (float)((double)lx - stx);
   const float ky = (float)((double)ly - sty);
   if (kp_hm) {
-    kp_hm[2 * i] = kx;
-    kp_hm[2 * i + 1] = ky;
+    kp_hm[2 * t] = kx;
+    kp_hm[2 * t + 1] = ky;
   }
   const double ix = (double)kx / (double)(WW - 1) * (double)in_w;
   const double iy = (double)ky / (double)(HH - 1) * (double)in_h;
   const float s0 = scale[2 * n], s1 = scale[2 * n + 1];
   const float h0 = 0.5f * s0, h1 = 0.5f * s1;
-  kp_img[2 * i] = ix / (double)in_w * (double)s0 + (double)center[2 * n] - (double)h0;
-  kp_img[2 * i + 1] = iy / (double)in_h * (double)s1 + (double)center[2 * n + 1] - (double)h1;
+  kp_img[2 * t] = ix / (double)in_w * (double)s0 + (double)center[2 * n] - (double)h0;
+  kp_img[2 * t + 1] = iy / (double)in_h * (double)s1 + (double)center[2 * n + 1] - (double)h1;
 }
 
 int udp_decode(const float* avg, int n, int joints, int h, int w, const float* center, const float* scale, int in_w,
                int in_h, float* work, double* kp_img, float* score, int32_t* argmax, float* kp_hm, hipStream_t s) {
   if (n <= 0) return 0;
   const size_t lds = (size_t)(h * w + (h + 10) * w) * sizeof(float);
-  hipLaunchKernelGGL(decode_blur_kernel, dim3(n * joints), dim3(256), lds, s, avg, joints, h, w, work, argmax, score);
+  hipLaunchKernelGGL(decode_blur_kernel, dim3(n * joints), dim3(256), lds, s, avg, h, w, work, argmax, score);
   const int tot = n * joints;
-  hipLaunchKernelGGL(decode_refine_kernel, dim3((tot + 127) / 128), dim3(128), 0, s, work, argmax, score, n, joints, h,
-                     w, center, scale, in_w, in_h, kp_img, kp_hm);
+  hipLaunchKernelGGL(decode_refine_kernel<false>, dim3((tot + 127) / 128), dim3(128), 0, s, work, argmax, score, n,
+                     joints, 1, h, w, center, scale, in_w, in_h, kp_img, kp_hm);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int udp_decode_topk(const float* avg, int n, int joints, int h, int w, const float* center, const float* scale,
+                    int in_w, int in_h, int n_cand, int min_sep, float min_score, float* work, double* kp_img,
+                    float* score, int32_t* peak, float* kp_hm, hipStream_t s) {
+  if (n <= 0) return 0;
+  if (n_cand < 1 || n_cand > CAND_MAX) return -2;
+  const size_t lds = (size_t)(h * w + (h + 10) * w) * sizeof(float);
+  hipLaunchKernelGGL(topk_blur_kernel, dim3(n * joints), dim3(256), lds, s, avg, h, w, n_cand, min_sep, min_score,
+                     work, peak, score);
+  const int tot = n * joints * n_cand;
+  hipLaunchKernelGGL(decode_refine_kernel<true>, dim3((tot + 127) / 128), dim3(128), 0, s, work, peak, score, n,
+                     joints, n_cand, h, w, center, scale, in_w, in_h, kp_img, kp_hm);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

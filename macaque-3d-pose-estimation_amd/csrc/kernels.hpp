@@ -101,6 +101,10 @@ int flip_average(const float* hm_all, float* avg, int n, int joints, int h, int 
 int udp_decode(const float* avg, int n, int joints, int h, int w, const float* center, const float* scale,
                int in_w, int in_h, float* work, double* kp_img, float* score, int32_t* argmax, float* kp_hm,
                hipStream_t s);
+// up to n_cand <= CAND_MAX (candidates.hpp) peaks per (instance, joint); outputs gain a slot axis
+int udp_decode_topk(const float* avg, int n, int joints, int h, int w, const float* center, const float* scale,
+                    int in_w, int in_h, int n_cand, int min_sep, float min_score, float* work, double* kp_img,
+                    float* score, int32_t* peak, float* kp_hm, hipStream_t s);
 
 // optim_points (optim.hip)
 extern int g_optim_pcg_iters;

@@ -85,18 +85,7 @@ class VitPoseHip:
         if n_candidates is not None:
             return decode_heatmaps_topk(heatmaps, center, scale, n_candidates, min_sep=min_sep,
                                         min_score=min_score, device=self.device)
-        n, J, hh, ww = heatmaps.shape
-        heatmaps = heatmaps.contiguous()
-        kp = torch.empty((n, J, 2), device=self.dev, dtype=torch.float64)
-        score = torch.empty((n, J), device=self.dev, dtype=torch.float32)
-        am = torch.empty((n, J), device=self.dev, dtype=torch.int32)
-        kp_hm = torch.empty((n, J, 2), device=self.dev, dtype=torch.float32)
-        center, scale = center.contiguous(), scale.contiguous()
-        _lib.check(self.lib.mq_decode_udp(self.ctx.handle, _lib.ptr(heatmaps), n, J, hh, ww,
-                                          _lib.ptr(center), _lib.ptr(scale), _lib.ptr(kp),
-                                          _lib.ptr(score), _lib.ptr(am), _lib.ptr(kp_hm), _lib.stream_ptr(self.dev)),
-                   "mq_decode_udp")
-        return kp, score, am, kp_hm
+        return decode_heatmaps(heatmaps, center, scale, device=self.device)
 
     def topdown(self, frames, boxes, box_frame, flip_test=True, n_candidates=None):
         """inference_topdown over every box of every view in one batch (``n_candidates``: see decode)."""

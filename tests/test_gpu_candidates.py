@@ -111,6 +111,36 @@ def test_decode_topk(case, K, min_score):
             np.testing.assert_allclose(kp[i, ok, k], ref_img[k, ok], rtol=0, atol=2e-2)
 
 
+def test_decode_slot0_edge_maps():
+    """NaN pixels and an all-equal map through the argmax reduction that both decodes share: slot 0 stays the
+    single-candidate result bit for bit (NaN in the same places), the argmax is np.argmax's."""
+    import torch
+    from cand_ref import topk_peaks
+    from mqhip.pose import decode_heatmaps, decode_heatmaps_topk
+    rng = np.random.default_rng(21)
+    hm = rng.normal(0, 0.02, (1, 3, 20, 12)).astype(np.float32)
+    hm[0, 0, 7, 5] = hm[0, 0, 11, 2] = np.nan       # the first NaN is the argmax: 7 * 12 + 5
+    hm[0, 1] = 0.25                                   # every pixel ties: index 0
+    center = rng.uniform(100, 1500, (1, 2)).astype(np.float32)
+    scale = rng.uniform(50, 400, (1, 2)).astype(np.float32)
+    dev = [torch.from_numpy(a).cuda() for a in (hm, center, scale)]
+    one = [t.cpu().numpy() for t in decode_heatmaps(*dev)]
+    want = [int(np.argmax(hm[0, j].reshape(-1))) for j in range(3)]
+    assert want[:2] == [89, 0]
+    np.testing.assert_array_equal(one[2][0], want)
+    for K in (1, 2, 3, 4):
+        kp, score, peak, kp_hm = [t.cpu().numpy() for t in decode_heatmaps_topk(*dev, K)]
+        for got, ref in zip((kp, score, peak, kp_hm), one):
+            np.testing.assert_array_equal(got[:, :, 0], ref)
+        np.testing.assert_array_equal(peak[0, :, 0], want)
+        for j in range(3):
+            rpeak, rscore = topk_peaks(hm[0, j], K)
+            np.testing.assert_array_equal(peak[0, j], rpeak)
+            np.testing.assert_array_equal(score[0, j], rscore)
+        assert (peak[0, :2, 1:] == -1).all() and (score[0, :2, 1:] == 0).all()   # NaN maximum / one plateau
+        assert np.isnan(score[0, 0, 0]) and score[0, 1, 0] == np.float32(0.25)
+
+
 def test_decode_topk_model_api_default_unchanged():
     import torch
     from mqhip.pose import VitPoseHip
@@ -342,6 +372,70 @@ def test_triangulate_possible_p1_equals_ransac():
         b = g.triangulate_possible(pts[:, :, None], min_cams=min_cams)
         for x, y in zip(a, b):
             np.testing.assert_array_equal(x, y)
+
+
+def _nine_camera_scene():
+    """C = 9 (the MAXC = 16 kernel instances), N = 12, P = 2, the points of _tri_scene: each is seen by camera 8
+    and three of cameras 0..7, point 0 by none.  Returns g, o, the true-slot points (9, 12, 2) and all
+    candidates (9, 12, 2, 2)."""
+    key = "nine"
+    if key in _TRI:
+        return _TRI[key]
+    from mqhip import synth
+    from mqhip.geometry import CameraGroup
+    from oracle.geometry import CameraGroupOracle
+    C, N, P = 9, 12, 2
+    cams = synth.make_cameras(C)
+    g, o = CameraGroup.from_dicts(cams), CameraGroupOracle(cams)
+    X = synth.make_skeletons(1, 1).reshape(-1, 3)[:N]
+    rng = np.random.default_rng(100 * C + 10 * P + N)
+    uv = o.project(X)                                                        # (C, N, 2)
+    true = uv + rng.normal(0, 0.2, uv.shape)
+    pts = uv[:, :, None, :] + rng.normal(0, 60, (C, N, P, 2))
+    slot = rng.integers(0, P, (C, N))
+    ci, ni = np.meshgrid(np.arange(C), np.arange(N), indexing="ij")
+    pts[ci, ni, slot] = true
+    seen = np.zeros((C, N), dtype=bool)
+    seen[8] = True
+    for n in range(N):
+        seen[rng.choice(8, 3, replace=False), n] = True
+    seen[:, 0] = False
+    pts[~seen] = np.nan
+    true[~seen] = np.nan
+    _TRI[key] = (g, o, true, pts)
+    return _TRI[key]
+
+
+def test_ransac_nine_cameras():
+    g, o, pts, _ = _nine_camera_scene()
+    for min_cams in (2, 3):
+        p3, picked, p2, err = g.triangulate_ransac(pts, min_cams=min_cams)
+        r3, rpicked, r2, rerr = o.triangulate_ransac(pts, min_cams=min_cams)
+        np.testing.assert_array_equal(picked, rpicked)
+        assert np.array_equal(np.isnan(p3), np.isnan(r3))
+        np.testing.assert_allclose(p3, r3, rtol=0, atol=1e-6, equal_nan=True)
+        np.testing.assert_allclose(err, rerr, rtol=1e-9, atol=1e-9)
+        np.testing.assert_array_equal(p2, r2)
+        assert np.isnan(r3[0]).all() and np.isfinite(r3[1:]).all() and rpicked[8, 1:].all()   # the scene
+
+
+def test_possible_nine_cameras():
+    g, o, one, pts = _nine_camera_scene()
+    C, N, P = pts.shape[:3]
+    for min_cams in (2, 3):
+        a = g.triangulate_ransac(one, min_cams=min_cams)
+        b = g.triangulate_possible(one[:, :, None], min_cams=min_cams)
+        for x, y in zip(a, b):
+            np.testing.assert_array_equal(x, y)
+        p3, picked, p2, err = g.triangulate_possible(pts, min_cams=min_cams)
+        r3, rpicked, r2, rerr = o.triangulate_possible(pts, min_cams=min_cams)
+        assert picked.shape == (C, N, P) and picked.dtype == bool
+        np.testing.assert_array_equal(picked, rpicked)
+        np.testing.assert_array_equal(p2, r2)
+        assert np.array_equal(np.isnan(p3), np.isnan(r3))
+        np.testing.assert_allclose(p3, r3, rtol=0, atol=1e-6, equal_nan=True)
+        np.testing.assert_allclose(err, rerr, rtol=1e-9, atol=1e-9)
+        assert np.isnan(p3[0]).all() and not picked[:, 0].any() and (picked.sum(axis=2) <= 1).all()
 
 
 def test_triangulate_possible_limits():

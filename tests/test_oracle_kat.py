@@ -130,6 +130,11 @@ def test_gaussian_table_matches_hip_constants():
     body = body[:body.index("};")]
     vals = np.array([float(v) for v in re.findall(r"([0-9.]+(?:e-?[0-9]+)?)f", body)], dtype=np.float32)
     np.testing.assert_array_equal(vals, gaussian_kernel_1d(11))
+    # one table: both decode paths (single and top-K) live in imgproc.hip and read kGauss11
+    csrc = os.path.join(os.path.dirname(__file__), "..", "macaque-3d-pose-estimation_amd", "csrc")
+    hits = sum(open(os.path.join(csrc, f)).read().count("0.2005654126405716f") for f in sorted(os.listdir(csrc))
+               if os.path.isfile(os.path.join(csrc, f)))
+    assert hits == 1, hits
 
 
 def test_crop_constant_image_is_constant_inside():

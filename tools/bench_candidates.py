@@ -1,4 +1,4 @@
-"""The three candidate entry points (csrc/candidates.hip) at the sizes DESIGN.md section 8.7 reports, each beside
+"""The three candidate entry points (csrc/imgproc.hip, csrc/candidates.hip) at the sizes DESIGN.md section 8.7 reports, each beside
 its single-candidate counterpart on the same data, on one MI355X.  Call times are HIP events around the
 library calls on device-resident inputs (one JSON object on stdout); kernel times come from a run of its own
 under the profiler:  rocprofv3 --kernel-trace --stats -- python tools/bench_candidates.py --reps 3
