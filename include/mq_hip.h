@@ -29,6 +29,7 @@
 #ifndef MQ_HIP_H
 #define MQ_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -637,6 +638,34 @@ int mq_overlay_render(mq_ctx* ctx, const double* cams, int n_cams, const int32_t
 int mq_bundle_adjust(mq_ctx* ctx, int mode, int n_cams, int n_points, double* cam_params, double* points3d,
                      const double* obs, const uint8_t* use, int fix_cam0, double ftol, double xtol, int max_iter,
                      double* resid, double* info, void* stream);
+
+/* ---- Motion-JPEG frames (csrc/jpeg.hip): a baseline JPEG encoder for the overlay frames, so that only the
+ * compressed stream leaves the device.  tests/jpeg_ref.py is the numpy restatement, equal byte for byte: integer
+ * arithmetic only, no atomics on global memory, the same bits on every call.
+ *
+ * The codec: 8-bit baseline sequential DCT, YCbCr 4:2:0 (JFIF colour; chroma (a + b + c + d + bias) >> 2 with
+ * bias 1 / 2 in even / odd chroma columns, libjpeg's h2v2 rule), one interleaved scan, H and W padded to multiples of 16 by edge replication (SOF0 carries the true size), the matrix DCT
+ * A = (T X + 1024) >> 11, B = A T^T with T = rint(8192 c_u / 2 cos((2x + 1) u pi / 16)), quantisation
+ * q = sign(B) ((|B| + (Q << 14)) / (Q << 15)) with the Annex K tables under libjpeg's quality scaling, the four
+ * Annex K Huffman tables, and a restart marker every restart_interval MCUs (the intervals are coded in parallel).
+ * Header: SOI, APP0 (JFIF 1.01), DQT x 2, SOF0, DHT x 4, DRI, SOS: 629 bytes.
+ *
+ * mq_jpeg_max_bytes: the worst case of one frame's stream, header included (host only, no device call); 0 for
+ * arguments outside the bounds below.  A block codes at most 20 + 63 * 26 = 1658 bits (DC: a code of at most 9
+ * bits + 11 extra bits; 63 AC: a code of at most 16 bits + 10 extra bits each; a ZRL only replaces 16
+ * coefficients by at most 11 bits).  An interval of RI MCUs is padded to a byte: at most ceil(RI * 6 * 1658 / 8)
+ * bytes, twice that when every byte is stuffed, and one two-byte marker (RSTn, or EOI after the last) follows it:
+ *   629 + ceil(n_mcu / RI) * (2 * ceil(RI * 6 * 1658 / 8) + 2),  n_mcu = ceil(H / 16) * ceil(W / 16). */
+size_t mq_jpeg_max_bytes(int height, int width, int restart_interval);
+
+/* Encode n frames: frames uint8 BGR (height, width, 3), frame i at frames + i * frame_stride (bytes, device);
+ * frame i's complete JPEG is out[i * out_stride : + out_size[i]] (device; out_size int32 (n), device).  Nothing is
+ * written past out_size[i] within a slot.  height, width in [1, 65535], quality in [1, 100], restart_interval in
+ * [1, 32], n in [0, 65535]; out_stride < mq_jpeg_max_bytes (or a worst case beyond 2^31 - 1 bytes) returns -2.
+ * Stream-ordered: no host round trip inside the call; the context's workspace grows on the first call of a size. */
+int mq_jpeg_encode(mq_ctx* ctx, const uint8_t* frames, int64_t frame_stride, int n, int height, int width,
+                   int quality, int restart_interval, uint8_t* out, int64_t out_stride, int32_t* out_size,
+                   void* stream);
 
 #ifdef __cplusplus
 }

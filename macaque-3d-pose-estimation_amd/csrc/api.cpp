@@ -20,6 +20,7 @@
 #include "cmc.hpp"
 #include "geometry.hpp"
 #include "overlay.hpp"
+#include "jpeg.hpp"
 #include "detector.hpp"
 #include "idcls.hpp"
 #include "kernels.hpp"
@@ -86,6 +87,7 @@ struct mq_ctx {
   DevBuf det_ws;    // detector post-processing (sort, NMS masks)
   DevBuf dlt_ws;    // mq_triangulate_dlt: undistorted points
   DevBuf ba_ws;     // mq_bundle_adjust: per-observation blocks, partials, trial points
+  DevBuf jpeg_ws;   // mq_jpeg_encode: coefficients, per-interval slots, lengths, offsets
   mq::SiftWs* sift_ws = nullptr;  // SIFT pyramid + candidates of the stage entry points (mq_sift_*)
 };
 
@@ -243,6 +245,7 @@ int mq_destroy(mq_ctx* ctx) {
   ctx->assoc_ws.release();
   ctx->dlt_ws.release();
   ctx->ba_ws.release();
+  ctx->jpeg_ws.release();
   ctx->det_ws.release();
   mq::sift_ws_destroy(ctx->sift_ws);
   delete ctx;
@@ -1671,6 +1674,38 @@ int mq_overlay_render(mq_ctx* ctx, const double* cams, int C, const int32_t* cam
   if (rc || n_img == 0) return rc;
   K_TRY(mq::overlay_draw(frames, frame_stride, n_src, src_index, n_img, height, width, A, J, P, mrksize, prim_i,
                          prim_d, out, (hipStream_t)stream));
+  return 0;
+}
+
+// ----------------------------------------------------------------------------- Motion-JPEG frames
+size_t mq_jpeg_max_bytes(int height, int width, int restart_interval) {
+  return mq::jpeg_max_bytes(height, width, restart_interval);
+}
+
+int mq_jpeg_encode(mq_ctx* ctx, const uint8_t* frames, int64_t frame_stride, int n, int height, int width, int quality,
+                   int restart_interval, uint8_t* out, int64_t out_stride, int32_t* out_size, void* stream) {
+  if (!ctx) return fail("mq_jpeg_encode: null ctx");
+  if (height < 1 || height > 65535 || width < 1 || width > 65535)
+    return fail("mq_jpeg_encode: height and width must be in [1, 65535]", -2);
+  if (quality < 1 || quality > 100) return fail("mq_jpeg_encode: quality must be in [1, 100]", -2);
+  if (restart_interval < 1 || restart_interval > mq::JPEG_MAX_RI)
+    return fail("mq_jpeg_encode: restart_interval must be in [1, 32]", -2);
+  if (n < 0 || n > 65535) return fail("mq_jpeg_encode: n must be in [0, 65535]", -2);
+  const size_t need = mq::jpeg_max_bytes(height, width, restart_interval);
+  if (need > (size_t)INT32_MAX) return fail("mq_jpeg_encode: the worst-case stream exceeds 2^31 - 1 bytes", -2);
+  if (out_stride < (int64_t)need) return fail("mq_jpeg_encode: out_stride is below mq_jpeg_max_bytes", -2);
+  if (frame_stride < (int64_t)height * width * 3) return fail("mq_jpeg_encode: frame_stride is below one frame", -2);
+  if (n == 0) return 0;
+  if (!frames || !out || !out_size) return fail("mq_jpeg_encode: null argument");
+  mq::JpegHeader hdr;
+  mq::JpegQuant q;
+  if (mq::jpeg_make_header(height, width, quality, restart_interval, hdr, q))
+    return fail("mq_jpeg_encode: header construction failed", -6);
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (ctx->jpeg_ws.ensure(mq::jpeg_workspace_bytes(n, height, width, restart_interval)))
+    return fail("mq_jpeg_encode: out of device memory", -5);
+  K_TRY(mq::jpeg_encode(frames, frame_stride, n, height, width, restart_interval, hdr, q, out, out_stride, out_size,
+                        ctx->jpeg_ws.p, (hipStream_t)stream));
   return 0;
 }
 

@@ -9,6 +9,7 @@
   strings, numbers, booleans and nested lists).
 * ``alldata.json`` / ``frame_num.npy`` (step1_proc2d.py:364-375): plain JSON / npy.
 * ``FrameStore``: the per-camera frame source of step 1 (stands in for imgstore).
+* ``MjpegAviWriter`` / ``MjpegAviReader``: the Motion-JPEG AVI the overlay stage writes with ``video='avi'``.
 """
 from __future__ import annotations
 
@@ -224,3 +225,178 @@ class FrameStoreWriter:
         with open(os.path.join(d, "metadata.yaml"), "w") as f:
             yaml.safe_dump({"__store": {"camera_id": str(self.camera_id), "imgshape": list(self.shape),
                                         "format": "npy"}}, f)
+
+
+# ----------------------------------------------------------------------------- Motion-JPEG AVI
+_AVIF_HASINDEX = 0x10
+_AVIIF_KEYFRAME = 0x10
+_AVI_MOVI_FOURCC_AT = 220      # RIFF 12 + LIST hdrl 12 + avih 64 + LIST strl 12 + strh 64 + strf 48 + LIST movi 8
+
+
+def mjpeg_avi_files(path):
+    """The files of one recording in order: ``path`` and its rollover files ``<stem>.001.avi``, ..."""
+    stem, out, k = os.path.splitext(str(path))[0], [str(path)], 1
+    while os.path.exists(f"{stem}.{k:03d}.avi"):
+        out.append(f"{stem}.{k:03d}.avi")
+        k += 1
+    return out
+
+
+class MjpegAviWriter:
+    """Motion-JPEG AVI (AVI 1.0, one ``vids`` / ``MJPG`` stream, ``idx1`` index); every frame is a complete JPEG.
+
+      RIFF 'AVI ' | LIST hdrl ( avih 56 bytes, AVIF_HASINDEX | LIST strl ( strh 56 bytes | strf 40 bytes ) )
+                  | LIST movi ( 00dc chunks, padded to even length ) | idx1 (16 bytes per frame: 00dc,
+                    AVIIF_KEYFRAME, offset from the movi fourcc, size)
+
+    Sizes and counts are patched by ``close``.  A file that the next frame would take past ``max_bytes`` is closed
+    and writing continues in ``<stem>.001.avi``, ``<stem>.002.avi``, ... (AVI 1.0 sizes are 32 bits; OpenDML is not
+    written).  Frame numbers / times given to ``append`` are written by ``close`` as ``<stem>.frame_number.npy`` /
+    ``<stem>.frame_time.npy`` beside the first file (the frame mapping a frame store keeps)."""
+
+    def __init__(self, path, height, width, fps=24.0, max_bytes=2 ** 31 - 2 ** 20):
+        from fractions import Fraction
+        path = str(path)
+        if not path.endswith(".avi"):
+            raise ValueError(f"path must end in .avi, got {path}")
+        if not (1 <= int(height) <= 65535 and 1 <= int(width) <= 65535):
+            raise ValueError("height and width must be in [1, 65535]")
+        if not float(fps) > 0:
+            raise ValueError(f"fps must be positive, got {fps}")
+        if not _AVI_MOVI_FOURCC_AT + 4 < int(max_bytes) < 2 ** 32:
+            raise ValueError("max_bytes must be in (224, 2^32)")
+        self.path, self.stem = path, path[:-4]
+        self.H, self.W, self.fps, self.max_bytes = int(height), int(width), float(fps), int(max_bytes)
+        rate = Fraction(self.fps).limit_denominator(100000)
+        self.rate, self.scale = rate.numerator, rate.denominator
+        self.paths, self.n_total = [], 0
+        self.frame_number, self.frame_time = [], []
+        self._f = None
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        self._open()
+
+    def _header(self, n_frames, movi_bytes, max_chunk):
+        import struct
+        avih = struct.pack("<14I", int(round(1e6 * self.scale / self.rate)), 0, 0, _AVIF_HASINDEX, n_frames, 0, 1,
+                           max_chunk, self.W, self.H, 0, 0, 0, 0)
+        strh = struct.pack("<4s4sIHHIIIIIIII4h", b"vids", b"MJPG", 0, 0, 0, 0, self.scale, self.rate, 0, n_frames,
+                           max_chunk, 0xFFFFFFFF, 0, 0, 0, min(self.W, 32767), min(self.H, 32767))
+        strf = struct.pack("<IiiHH4sIiiII", 40, self.W, self.H, 1, 24, b"MJPG", self.W * self.H * 3, 0, 0, 0, 0)
+        chunk = lambda cc, d: cc + struct.pack("<I", len(d)) + d
+        strl = b"LIST" + struct.pack("<I", 4 + 64 + 48) + b"strl" + chunk(b"strh", strh) + chunk(b"strf", strf)
+        hdrl = b"LIST" + struct.pack("<I", 4 + 64 + len(strl)) + b"hdrl" + chunk(b"avih", avih) + strl
+        riff = 4 + len(hdrl) + 8 + 4 + movi_bytes + 8 + 16 * n_frames
+        h = b"RIFF" + struct.pack("<I", riff) + b"AVI " + hdrl + b"LIST" + struct.pack("<I", 4 + movi_bytes) + b"movi"
+        assert len(h) == _AVI_MOVI_FOURCC_AT + 4
+        return h
+
+    def _open(self):
+        k = len(self.paths)
+        p = self.path if k == 0 else f"{self.stem}.{k:03d}.avi"
+        self.paths.append(p)
+        self._f = open(p, "wb")
+        self._f.write(self._header(0, 0, 0))
+        self._index, self._movi, self._max_chunk = [], 0, 0      # (offset, size) per frame; bytes of chunks
+
+    def _finish(self):
+        import struct
+        f = self._f
+        f.write(b"idx1" + struct.pack("<I", 16 * len(self._index)))
+        for off, size in self._index:
+            f.write(struct.pack("<4sIII", b"00dc", _AVIIF_KEYFRAME, off, size))
+        f.seek(0)
+        f.write(self._header(len(self._index), self._movi, self._max_chunk))
+        f.close()
+        self._f = None
+
+    def append(self, jpeg_bytes, frame_number=None, frame_time=None):
+        import struct
+        if self._f is None:
+            raise ValueError("the writer is closed")
+        data = bytes(jpeg_bytes)
+        chunk = 8 + len(data) + (len(data) & 1)
+        size_after = _AVI_MOVI_FOURCC_AT + 4 + self._movi + chunk + 8 + 16 * (len(self._index) + 1)
+        if size_after > self.max_bytes:
+            if not self._index:
+                raise ValueError(f"a frame of {len(data)} bytes does not fit a file of max_bytes {self.max_bytes}")
+            self._finish()
+            self._open()
+        self._index.append((4 + self._movi, len(data)))
+        self._f.write(b"00dc" + struct.pack("<I", len(data)) + data + (b"\x00" if len(data) & 1 else b""))
+        self._movi += chunk
+        self._max_chunk = max(self._max_chunk, len(data))
+        self.n_total += 1
+        if frame_number is not None:
+            self.frame_number.append(int(frame_number))
+        if frame_time is not None:
+            self.frame_time.append(float(frame_time))
+
+    def close(self):
+        if self._f is None:
+            return
+        self._finish()
+        for name, vals, dt in (("frame_number", self.frame_number, np.int64), ("frame_time", self.frame_time,
+                                                                               np.float64)):
+            if vals:
+                if len(vals) != self.n_total:
+                    raise ValueError(f"{name} was given for {len(vals)} of {self.n_total} frames")
+                np.save(f"{self.stem}.{name}.npy", np.asarray(vals, dtype=dt))
+
+
+class MjpegAviReader:
+    """One file an ``MjpegAviWriter`` wrote, through its ``idx1`` index: ``len()``, ``frame_bytes(i)``, ``fps``,
+    ``width``, ``height``.  (``mjpeg_avi_files`` lists a recording's rollover files.)"""
+
+    def __init__(self, path):
+        import struct
+        self.path = str(path)
+        with open(self.path, "rb") as f:
+            self._data = f.read()
+        d = self._data
+        if d[:4] != b"RIFF" or d[8:12] != b"AVI ":
+            raise ValueError(f"{path}: not a RIFF AVI file")
+        if struct.unpack_from("<I", d, 4)[0] + 8 != len(d):
+            raise ValueError(f"{path}: RIFF size does not match the file (not closed?)")
+        self.chunks = {}
+        self._walk(12, len(d))
+        for need in ("avih", "strh", "strf", "movi", "idx1"):
+            if need not in self.chunks:
+                raise ValueError(f"{path}: no {need} chunk")
+        avih = struct.unpack_from("<14I", d, self.chunks["avih"][0])
+        strh = struct.unpack_from("<4s4sIHHIIIIIIII4h", d, self.chunks["strh"][0])
+        strf = struct.unpack_from("<IiiHH4sIiiII", d, self.chunks["strf"][0])
+        if strh[0] != b"vids" or strh[1] != b"MJPG" or strf[5] != b"MJPG":
+            raise ValueError(f"{path}: not a Motion-JPEG video stream")
+        self.avih, self.strh, self.strf = avih, strh, strf
+        self.width, self.height = int(strf[1]), int(strf[2])
+        self.fps = strh[7] / strh[6]
+        off, size = self.chunks["idx1"]
+        self.movi_at = self.chunks["movi"][0] - 4          # the movi fourcc
+        self.index = [struct.unpack_from("<4sIII", d, off + 16 * i) for i in range(size // 16)]
+        if len(self.index) != avih[4] or len(self.index) != strh[9]:
+            raise ValueError(f"{path}: idx1 has {len(self.index)} entries, the headers say {avih[4]} / {strh[9]}")
+
+    def _walk(self, pos, end):
+        import struct
+        d = self._data
+        while pos + 8 <= end:
+            cc, size = d[pos:pos + 4], struct.unpack_from("<I", d, pos + 4)[0]
+            if cc == b"LIST":
+                kind = d[pos + 8:pos + 12].decode("latin1")
+                self.chunks[kind] = (pos + 12, size - 4)
+                if kind != "movi":
+                    self._walk(pos + 12, pos + 8 + size)
+            else:
+                self.chunks.setdefault(cc.decode("latin1"), (pos + 8, size))
+            pos += 8 + size + (size & 1)
+
+    def __len__(self):
+        return len(self.index)
+
+    def frame_bytes(self, i):
+        import struct
+        cc, flags, off, size = self.index[i]
+        at = self.movi_at + off
+        if self._data[at:at + 4] != b"00dc" or struct.unpack_from("<I", self._data, at + 4)[0] != size:
+            raise ValueError(f"{self.path}: idx1 entry {i} does not point at a 00dc chunk of its size")
+        return self._data[at + 8:at + 8 + size]

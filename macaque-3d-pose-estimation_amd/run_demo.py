@@ -18,7 +18,8 @@ This build runs the same chain on MI355X with the parts outside its scope replac
 * step 4 (``src.pipeline.step4_aniposefiltering.proc``): unchanged drop-in;
 * visualisation (``src.pipeline.visualize_result.proc``, run_demo.py:33-39): opt-in through ``visualize``
   (``--visualize all`` or ``--visualize 0,3``); rank 0 renders the listed cameras on the GPU after step 4 into
-  ``<out_dir>/<data>_<camid>/`` frame stores (no video codec exists in this build).  The
+  ``<out_dir>/<data>_<camid>/`` frame stores, or with ``visualize_video="avi"`` (``--video avi``) into
+  ``<out_dir>/<data>_<camid>.avi`` Motion-JPEG files encoded on the GPU (DESIGN.md sections 3.7 and 8.8).  The
   default leaves the chain at ``kp3d.pickle``.  The ``pictorial`` import is not needed.
 
 Multi-GPU (BASELINE config 3): run one process per GPU under ``torch.distributed.run``; every rank
@@ -43,7 +44,7 @@ from src.pipeline import step4_aniposefiltering as step4
 def proc(data_name, fps, results_dir_root, device_str, config_path, raw_data_dir, n_kp, vidfile_prefix='',
          n_animal=4, track_to_animal=None, pose_model=None, id_model="auto", world=1, rank=0, group=None,
          sharded=False, gather_device=None, timings=None, association="known", visualize=None,
-         out_dir='./output'):
+         out_dir='./output', visualize_video=None, video_quality=90):
     """run_demo.py:21-30: step 1 -> (known assignment) -> step 4; returns step 4's kp3d dict (on rank 0;
     None on the other ranks of a sharded run).  ``timings``: optional dict filled with wall seconds per
     stage.
@@ -55,7 +56,8 @@ def proc(data_name, fps, results_dir_root, device_str, config_path, raw_data_dir
 
     ``visualize``: None (default: nothing is rendered, no output directory is made), "all" (every camera of
     ``camera_id``, as run_demo.py:33-39) or a list of camera indices; rank 0 renders them after step 4 into
-    ``out_dir`` (``src.pipeline.visualize_result.proc``).
+    ``out_dir`` (``src.pipeline.visualize_result.proc``); ``visualize_video="avi"`` makes them Motion-JPEG AVI
+    files at JPEG quality ``video_quality`` and ``fps`` instead of frame stores.
 
     Steps 3-4 take step 1's rows in memory (the files are still written, by a background thread joined
     before returning).  On a sharded run (``world`` > 1 or ``sharded``) rank r post-processes and writes
@@ -120,7 +122,8 @@ def proc(data_name, fps, results_dir_root, device_str, config_path, raw_data_dir
             if split:
                 _barrier(group)            # ... of the rank that owns the camera: every rank has joined its writer
         if visualize is not None and rank == 0:
-            _visualize(visualize, data_name, config_path, raw_data_dir, results_dir_root, out_dir, device)
+            _visualize(visualize, data_name, config_path, raw_data_dir, results_dir_root, out_dir, device,
+                       visualize_video, video_quality, fps)
     finally:
         if s1out is not None:
             s1out.wait()
@@ -133,7 +136,8 @@ def proc(data_name, fps, results_dir_root, device_str, config_path, raw_data_dir
     return out
 
 
-def _visualize(visualize, data_name, config_path, raw_data_dir, results_dir_root, out_dir, device):
+def _visualize(visualize, data_name, config_path, raw_data_dir, results_dir_root, out_dir, device, video=None,
+               quality=90, fps=24.0):
     """run_demo.py:33-39: one ``vis.proc`` per camera (every camera of ``camera_id`` for "all")."""
     import yaml
     from src.pipeline import visualize_result as vis
@@ -143,7 +147,7 @@ def _visualize(visualize, data_name, config_path, raw_data_dir, results_dir_root
     for i_cam in cams:
         print(f"[INFO] Generating overlay frames for camera {ID[i_cam]} (index {i_cam}) ...")
         vis.proc(data_name, i_cam, config_path, raw_data_dir, results_dir_root=results_dir_root, out_dir=out_dir,
-                 device=device)
+                 device=device, video=video, quality=quality, fps=float(fps))
 
 
 def _barrier(group):
@@ -194,12 +198,16 @@ if __name__ == '__main__':
     ap.add_argument("--visualize", default=None,
                     help="all, or camera indices i,j,...: render overlay frame stores after step 4 (default: none)")
     ap.add_argument("--out", default="./output", help="where --visualize writes <data>_<camid>/")
+    ap.add_argument("--video", choices=("avi",), default=None,
+                    help="avi: --visualize writes Motion-JPEG <data>_<camid>.avi files instead of frame stores")
+    ap.add_argument("--video-quality", type=int, default=90, help="JPEG quality of --video avi, 1..100")
     a = ap.parse_args()
     vis_arg = None if a.visualize is None else ("all" if a.visualize == "all" else
                                                 [int(i) for i in a.visualize.split(",")])
     W, R, L, G, dev = _dist_from_env()
     proc(a.data, a.fps, a.results, f"cuda:{L}", a.config, a.raw, a.n_kp, world=W, rank=R, group=G,
-         gather_device=dev, association=a.association, visualize=vis_arg, out_dir=a.out)
+         gather_device=dev, association=a.association, visualize=vis_arg, out_dir=a.out,
+         visualize_video=a.video, video_quality=a.video_quality)
     if W > 1:
         import torch.distributed as dist
         dist.barrier()

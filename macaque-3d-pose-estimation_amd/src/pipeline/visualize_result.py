@@ -4,10 +4,12 @@ camera, draw every animal's skeleton over the camera's frames, and write the res
 The drawing runs on the GPU (``mqhip.overlay.OverlayRenderer``: ``mq_overlay_render``, csrc/overlay.hip).
 Deviations from the reference, all stated in DESIGN.md section 8.5:
 
-* no video codec exists in this build (no cv2 / imageio / imgstore), so where the reference writes
-  ``<out>/<data>_<camid>.mp4`` this writes a frame store ``<out>/<data>_<camid>/`` that ``mqhip.io.FrameStore``
-  opens (``frames.npy`` uint8 (N, H, W, 3) BGR, ``frame_number.npy``, ``frame_time.npy``, ``metadata.yaml``, empty
-  ``tracks.json`` rows);
+* where the reference writes ``<out>/<data>_<camid>.mp4`` (cv2 / ffmpeg, neither of which this build has), the
+  default writes a frame store ``<out>/<data>_<camid>/`` that ``mqhip.io.FrameStore`` opens (``frames.npy`` uint8
+  (N, H, W, 3) BGR, ``frame_number.npy``, ``frame_time.npy``, ``metadata.yaml``, empty ``tracks.json`` rows), and
+  ``video='avi'`` writes a Motion-JPEG AVI ``<out>/<data>_<camid>.avi`` instead: the rendered frames are encoded
+  on the GPU by the project's own baseline JPEG encoder (``mqhip.mjpeg.JpegEncoder``: ``mq_jpeg_encode``,
+  csrc/jpeg.hip) and only the compressed streams leave the device (``mqhip.io.MjpegAviWriter``);
 * the discs and limbs are covered by the project's own exact rules, not by cv2's fixed-point rasterisers, and the
   limb angle is not rounded to whole degrees: edges may differ from cv2's by a pixel;
 * the cameras come from ``<result>/calibration.toml`` (what step 4 writes and reads), not from the h5 files.
@@ -30,8 +32,14 @@ def _gpu_renderer(cgroup, height, width, skeleton, mrksize, device):
     return OverlayRenderer(cgroup, height, width, skeleton=skeleton, mrksize=mrksize, device=device)
 
 
+def _gpu_encoder(height, width, quality, device):
+    from mqhip.mjpeg import JpegEncoder
+    return JpegEncoder(height, width, quality=quality, device=device)
+
+
 def proc(data_name, i_cam, config_path, raw_data_dir=None, results_dir_root='./results3D', out_dir='./output',
-         device=0, batch=16, step=1, frame_range=None, skeleton=None, mrksize=3, renderer=None):
+         device=0, batch=16, step=1, frame_range=None, skeleton=None, mrksize=3, renderer=None, video=None,
+         quality=90, fps=24.0, encoder=None):
     """visualize_result.py:136-254 for camera ``camera_id[i_cam]`` of ``config_path``.
 
     ``step`` / ``frame_range=(start, stop)`` select the rows ``range(start, stop, step)`` of kp3d's frame axis
@@ -39,7 +47,11 @@ def proc(data_name, i_cam, config_path, raw_data_dir=None, results_dir_root='./r
     the source images a batch needs are uploaded once (stores may keep a pool of images shared by many frames).
     ``renderer``: a factory ``(cgroup, height, width, skeleton, mrksize, device)`` of an object with
     ``OverlayRenderer.render``'s signature (tests inject the NumPy oracle); the default is the GPU renderer.
-    Returns the written store's directory, or None on the early returns."""
+    ``video``: None (default) writes the frame store; ``'avi'`` encodes every rendered batch on the device at JPEG
+    ``quality`` (the frames are not copied to the host) and writes ``<out>/<data>_<camid>.avi`` at ``fps`` with
+    ``<out>/<data>_<camid>.frame_number.npy`` / ``.frame_time.npy`` beside it.  ``encoder``: a factory
+    ``(height, width, quality=, device=)`` of an object with ``JpegEncoder.encode`` (tests inject the NumPy encoder).
+    Returns the written store's directory (or the AVI's path), or None on the early returns."""
     from mqhip import io as mqio
     from mqhip.geometry import CameraGroup
     skeleton = SKELETON if skeleton is None else skeleton
@@ -49,9 +61,13 @@ def proc(data_name, i_cam, config_path, raw_data_dir=None, results_dir_root='./r
         cfg = yaml.safe_load(f)
     ID = cfg['camera_id']
 
+    if video not in (None, 'avi'):
+        raise ValueError(f"video must be None or 'avi', got {video!r}")
     vid_path = os.path.join(out_dir, data_name + '_{:d}'.format(ID[i_cam]))
+    if video == 'avi':
+        vid_path += '.avi'
 
-    if os.path.exists(os.path.join(vid_path, 'metadata.yaml')):
+    if os.path.exists(vid_path if video == 'avi' else os.path.join(vid_path, 'metadata.yaml')):
         print('already exists:', vid_path)
         return None
 
@@ -90,7 +106,11 @@ def proc(data_name, i_cam, config_path, raw_data_dir=None, results_dir_root='./r
     H, W = (int(v) for v in store.frames.shape[1:3])
     cgroup = CameraGroup.load(result_dir + '/calibration.toml', device=device).subset_cameras_names([str(ID[i_cam])])
     draw = (renderer or _gpu_renderer)(cgroup, H, W, skeleton, mrksize, device)
-    writer = mqio.FrameStoreWriter(vid_path, len(rows), H, W, ID[i_cam])
+    if video == 'avi':
+        encode = (encoder or _gpu_encoder)(H, W, quality=quality, device=device)
+        writer = mqio.MjpegAviWriter(vid_path, H, W, fps=fps)
+    else:
+        writer = mqio.FrameStoreWriter(vid_path, len(rows), H, W, ID[i_cam])
     batch = max(1, int(batch))
     for k in range(0, len(rows), batch):
         part = rows[k:k + batch]
@@ -101,6 +121,10 @@ def proc(data_name, i_cam, config_path, raw_data_dir=None, results_dir_root='./r
         frames = np.stack([np.asarray(store.frames[int(p)]) for p in pool])      # each source image once
         out = draw.render(frames, 0, X[:, idx].transpose(1, 0, 2, 3), S[:, idx].transpose(1, 0, 2),
                           src_index=src_index.astype(np.int32))
+        if video == 'avi':
+            for jpg, fn, t in zip(encode.encode(out), fns, store.frame_time[pos]):
+                writer.append(jpg, fn, t)
+            continue
         out = out.cpu().numpy() if hasattr(out, 'cpu') else np.asarray(out)
         writer.append(out, fns, store.frame_time[pos])
     writer.close()
