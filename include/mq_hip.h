@@ -667,6 +667,85 @@ int mq_jpeg_encode(mq_ctx* ctx, const uint8_t* frames, int64_t frame_stride, int
                    int quality, int restart_interval, uint8_t* out, int64_t out_stride, int32_t* out_size,
                    void* stream);
 
+/* ---- Motion-JPEG decoding (csrc/jpeg_parse.cpp, csrc/jpeg_dec_dev.hpp, csrc/jpeg_dec.hip): the other half of the
+ * codec, so that a frame store holds compressed frames and only those cross the disk and the bus.
+ * tests/jpeg_dec_ref.py is the numpy restatement, equal byte for byte, and on every stream Pillow (libjpeg-turbo)
+ * accepts both equal Image.open(...).convert('RGB') on every pixel.  Integer arithmetic only, no data-dependent
+ * order: the same bits on every call.
+ *
+ * Accepted: SOF0, 8-bit samples; one interleaved scan over all components with Ss = 0, Se = 63, Ah = Al = 0;
+ * 1 component (written B = G = R) or 3 components YCbCr with chroma sampled 1x1 and luma 1x1, 2x1 or 2x2; DQT with
+ * Pq = 0, ids 0-3; DHT ids 0-1 per class (a DC symbol is at most 15); any DRI (0: no restart markers); APPn, COM
+ * and unknown segments with a length are skipped; a stream without any DHT uses the four Annex K tables; height and
+ * width in [1, 65535].  The first FF D9 after SOS ends the scan.
+ *
+ * mq_jpeg_parse (host only, no device call) fills *info and returns 0, or one of: */
+#define MQ_JPEG_E_NOT_JPEG (-20)   /* null / empty / no SOI, or a byte that is no marker where one must stand */
+#define MQ_JPEG_E_TRUNCATED (-21)  /* the header ends inside a segment, or a segment's length contradicts its content */
+#define MQ_JPEG_E_SOF (-22)        /* SOF1..SOF15 (extended, progressive, lossless, arithmetic), two SOF0, SOS before SOF0 */
+#define MQ_JPEG_E_PRECISION (-23)  /* samples of another precision than 8 bits */
+#define MQ_JPEG_E_DQT (-24)        /* Pq = 1 (16-bit table) or a table id above 3 */
+#define MQ_JPEG_E_COMPONENTS (-25) /* neither 1 nor 3 components, or an Adobe segment whose transform is not YCbCr */
+#define MQ_JPEG_E_SAMPLING (-26)   /* sampling factors other than 4:4:4, 4:2:2 (2x1) and 4:2:0 (2x2) */
+#define MQ_JPEG_E_SCANS (-27)      /* a scan over a subset of the components, Ss / Se / Ah / Al of another mode, or a
+                                      segment between the scan and EOI (several scans) */
+#define MQ_JPEG_E_TABLE (-28)      /* a component names a quantisation or Huffman table the stream never defined */
+#define MQ_JPEG_E_HUFFMAN (-29)    /* a DHT that is no prefix code (more than 256 symbols, or the canonical code
+                                      overflows its length), class / id above 1, a DC symbol above 15 */
+#define MQ_JPEG_E_NO_EOI (-30)     /* no FF D9 after the scan */
+#define MQ_JPEG_E_SIZE (-31)       /* height or width 0 */
+
+typedef struct mq_jpeg_huff {
+  uint8_t bits[16];   /* codes of length 1..16 */
+  uint8_t vals[256];  /* symbols in code order, zero past the last */
+} mq_jpeg_huff;
+
+/* Everything of a header the kernels need: 1320 bytes, passed to them by value (nothing is uploaded). */
+typedef struct mq_jpeg_info {
+  int32_t height, width, n_comp;      /* n_comp 1 or 3 */
+  int32_t h_luma, v_luma;             /* 1x1, 2x1 or 2x2 (1x1 for one component) */
+  int32_t restart_interval;           /* MCUs; 0: the scan is one interval */
+  int64_t scan_offset;                /* the first entropy-coded byte */
+  uint8_t quant[3][64];               /* per component, natural order */
+  uint8_t dc_sel[3], ac_sel[3];       /* per component: which of dc[] / ac[] */
+  uint8_t reserved[2];
+  mq_jpeg_huff dc[2], ac[2];
+} mq_jpeg_info;
+
+int mq_jpeg_parse(const uint8_t* bytes, int64_t size, mq_jpeg_info* info);
+
+/* Decode n streams that share one header (info; their first info->scan_offset bytes are taken as read): stream i is
+ * streams[i * stream_stride : + sizes[i]] -- mq_jpeg_encode's out / out_size layout, so encode -> decode chains on
+ * the device -- and its frame, uint8 BGR (height, width, 3), is written at frames + i * frame_stride.  Every
+ * pointer except info is a device pointer.  frame_stride < height * width * 3 returns -2, as do n outside
+ * [0, 65535], an info that mq_jpeg_parse could not have filled, and a workspace beyond 2^40 bytes.  Stream-ordered:
+ * no host round trip inside the call; the context's workspace grows on the first call of a size.
+ *
+ * Entropy decoding: bits MSB first; FF 00 unstuffs to FF (an FF before any other byte stays data); FF D0..D7 and
+ * FF D9 end a restart interval wherever they stand; interval i must end in D0 + (i mod 8) and the last of
+ * ceil(n_mcu / RI) (1 for RI 0) in D9; DC predictors start at 0 in every interval and are kept as int16 (wrapping);
+ * EXTEND is Annex F's (v < 2^(n-1) ? v - 2^n + 1 : v); AC symbol 0xF0 is ZRL, every other symbol of size 0 is EOB.
+ * One lane decodes one interval.  Dequantisation: coef[natural] = q[zigzag k] * Q[natural].
+ * IDCT: libjpeg's jpeg_idct_islow (CONST_BITS 13, PASS1_BITS 2; FIX constants 2446 3196 4433 6270 7373 9633 12299
+ * 15137 16069 16819 20995 25172), a column pass ((x + 1024) >> 11) and a row pass ((x + 131072) >> 18), + 128,
+ * clamp to [0, 255].  The 32-bit arithmetic is unsigned and WRAPS (the shifts are arithmetic on the wrapped
+ * value): defined for the huge coefficients a malformed stream can produce, and never reached by a valid one.
+ * Chroma upsampling: libjpeg's "fancy" rules on the true chroma extent ceil(H / v) x ceil(W / h), edges repeating
+ * the last true row / column.  h2v2: s = 3 cur + other (the row above for even output rows, below for odd ones),
+ * even column (3 s + s_left + 8) >> 4, odd column (3 s + s_right + 7) >> 4.  h2v1: even (3 c + c_left + 1) >> 2, odd
+ * (3 c + c_right + 2) >> 2.  A chroma plane at most 2 samples wide is replicated instead, in both modes.
+ * Colour, cb and cr less 128: R = Y + ((91881 cr + 32768) >> 16), G = Y + ((-22554 cb - 46802 cr + 32768) >> 16),
+ * B = Y + ((116130 cb + 32768) >> 16), clamped.
+ *
+ * status[i] (int32, device): 0 ok; 1 restart markers wrong in count or sequence, or no EOI (nothing of the frame
+ * is decoded); 2 bits that match no Huffman code; 3 a run past coefficient 63; 4 an interval's bits exhausted
+ * before its MCUs (also: no code matches and fewer than 16 bits are left).  An interval stops at its first fault;
+ * the status is the largest code among the frame's intervals.  Every scan-byte read is bounded by the interval's
+ * end and every coefficient index by 63.  A frame with a nonzero status leaves unspecified values inside its own
+ * height * width * 3 bytes, writes nothing outside them, and does not affect the other frames of the call. */
+int mq_jpeg_decode(mq_ctx* ctx, const uint8_t* streams, int64_t stream_stride, const int32_t* sizes, int n,
+                   const mq_jpeg_info* info, uint8_t* frames, int64_t frame_stride, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,7 @@
 #include "geometry.hpp"
 #include "overlay.hpp"
 #include "jpeg.hpp"
+#include "jpeg_dec.hpp"
 #include "detector.hpp"
 #include "idcls.hpp"
 #include "kernels.hpp"
@@ -88,6 +89,7 @@ struct mq_ctx {
   DevBuf dlt_ws;    // mq_triangulate_dlt: undistorted points
   DevBuf ba_ws;     // mq_bundle_adjust: per-observation blocks, partials, trial points
   DevBuf jpeg_ws;   // mq_jpeg_encode: coefficients, per-interval slots, lengths, offsets
+  DevBuf jpeg_dec_ws;  // mq_jpeg_decode: coefficients, component planes, interval ends
   mq::SiftWs* sift_ws = nullptr;  // SIFT pyramid + candidates of the stage entry points (mq_sift_*)
 };
 
@@ -246,6 +248,7 @@ int mq_destroy(mq_ctx* ctx) {
   ctx->dlt_ws.release();
   ctx->ba_ws.release();
   ctx->jpeg_ws.release();
+  ctx->jpeg_dec_ws.release();
   ctx->det_ws.release();
   mq::sift_ws_destroy(ctx->sift_ws);
   delete ctx;
@@ -1706,6 +1709,27 @@ int mq_jpeg_encode(mq_ctx* ctx, const uint8_t* frames, int64_t frame_stride, int
     return fail("mq_jpeg_encode: out of device memory", -5);
   K_TRY(mq::jpeg_encode(frames, frame_stride, n, height, width, restart_interval, hdr, q, out, out_stride, out_size,
                         ctx->jpeg_ws.p, (hipStream_t)stream));
+  return 0;
+}
+
+int mq_jpeg_decode(mq_ctx* ctx, const uint8_t* streams, int64_t stream_stride, const int32_t* sizes, int n,
+                   const mq_jpeg_info* info, uint8_t* frames, int64_t frame_stride, int32_t* status, void* stream) {
+  if (!ctx) return fail("mq_jpeg_decode: null ctx");
+  if (!info) return fail("mq_jpeg_decode: null info");
+  mq::JpegDecGeom g;
+  if (mq::jpeg_dec_geom(*info, g)) return fail("mq_jpeg_decode: info was not filled by mq_jpeg_parse", -2);
+  if (n < 0 || n > 65535) return fail("mq_jpeg_decode: n must be in [0, 65535]", -2);
+  if (frame_stride < (int64_t)g.H * g.W * 3) return fail("mq_jpeg_decode: frame_stride is below one frame", -2);
+  if (stream_stride < info->scan_offset || stream_stride > (int64_t)INT32_MAX)
+    return fail("mq_jpeg_decode: stream_stride must be in [scan_offset, 2^31 - 1]", -2);
+  if (n == 0) return 0;
+  if (!streams || !sizes || !frames || !status) return fail("mq_jpeg_decode: null argument");
+  const size_t need = mq::jpeg_dec_workspace_bytes(n, g);
+  if (need > ((size_t)1 << 40)) return fail("mq_jpeg_decode: the workspace exceeds 2^40 bytes", -2);
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (ctx->jpeg_dec_ws.ensure(need)) return fail("mq_jpeg_decode: out of device memory", -5);
+  K_TRY(mq::jpeg_decode(streams, stream_stride, sizes, n, *info, g, frames, frame_stride, status, ctx->jpeg_dec_ws.p,
+                        (hipStream_t)stream));
   return 0;
 }
 

@@ -29,7 +29,7 @@ EXPORTED = [
     "mq_tracklet_traces", "mq_tracklet_id_votes",
     "mq_overlay_primitives", "mq_overlay_render",
     "mq_bundle_adjust",
-    "mq_jpeg_encode",
+    "mq_jpeg_encode", "mq_jpeg_parse", "mq_jpeg_decode",
     "mq_decode_udp_topk", "mq_viterbi_filter_multi", "mq_triangulate_possible",
 ]
 
@@ -122,6 +122,8 @@ _SIGS = {
                                 vp, vp, vp, vp]),
     "mq_jpeg_max_bytes": (C.c_size_t, [i32, i32, i32]),     # size_t: not in EXPORTED (the int / char* entry points)
     "mq_jpeg_encode": (i32, [vp, vp, i64, i32, i32, i32, i32, i32, vp, i64, vp, vp]),
+    "mq_jpeg_parse": (i32, [vp, i64, vp]),                  # host only: no device call
+    "mq_jpeg_decode": (i32, [vp, vp, i64, vp, i32, vp, vp, i64, vp, vp]),
     "mq_bundle_adjust": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, i32, f64, f64, i32, vp, vp, vp]),
     "mq_decode_udp_topk": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, f32, vp, vp, vp, vp, vp]),
     "mq_viterbi_filter_multi": (i32, [vp, vp, i32, i32, i32, i32, i32, f64, i32, f64, vp, vp]),

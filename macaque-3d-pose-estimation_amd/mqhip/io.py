@@ -8,7 +8,8 @@
   subset of TOML the reference's ``toml.dump`` produces for these files (tables of
   strings, numbers, booleans and nested lists).
 * ``alldata.json`` / ``frame_num.npy`` (step1_proc2d.py:364-375): plain JSON / npy.
-* ``FrameStore``: the per-camera frame source of step 1 (stands in for imgstore).
+* ``FrameStore``: the per-camera frame source of step 1 (stands in for imgstore): raw ``frames.npy`` (``format:
+  npy``) or a Motion-JPEG ``frames.avi`` decoded on the GPU (``format: mjpeg``, ``convert_frame_store`` writes one).
 * ``MjpegAviWriter`` / ``MjpegAviReader``: the Motion-JPEG AVI the overlay stage writes with ``video='avi'``.
 """
 from __future__ import annotations
@@ -105,12 +106,18 @@ class FrameStore:
     """One camera's synchronized frames plus the detector/tracker output for them.
 
     Stands in for the reference's imgstore (``imgstore.new_for_filename(<raw>/<data>.<cam>/
-    metadata.yaml)``, step1_proc2d.py:403-408), which is not installable here and decodes video
-    this build does not handle.  Directory layout (``write_frame_store`` makes one):
+    metadata.yaml)``, step1_proc2d.py:403-408), which is not installable here and mostly decodes H.264,
+    which this build does not handle (its Motion-JPEG store format is what ``format: mjpeg`` mirrors).  Directory
+    layout (``write_frame_store`` makes an ``npy`` one, ``convert_frame_store`` an ``mjpeg`` one from it):
 
       metadata.yaml     imgstore-style metadata (camera id, image size); its presence is what
                         step 1 globs for, exactly like the reference
-      frames.npy        uint8 (N, H, W, 3) BGR, memory-mapped (never loaded whole)
+      frames.npy        uint8 (N, H, W, 3) BGR, memory-mapped (never loaded whole) -- stores of ``format: npy``
+      frames.avi        stores of ``format: mjpeg`` instead: the same images as baseline JPEG frames of a
+                        Motion-JPEG AVI (and its rollover files); ``frames`` is then an ``MjpegFrames`` that decodes
+                        on the GPU (``decoder``: a factory ``(device=)`` of an object with ``JpegDecoder.decode``;
+                        tests inject the NumPy decoder) on ``device``, so only compressed bytes cross the disk
+                        and the bus
       frame_time.npy    float64 (N,)  -- get_frame_metadata()["frame_time"]
       frame_number.npy  int64 (N,)    -- get_frame_metadata()["frame_number"]
       tracks.json       per stored frame, the tracker rows [x1, y1, x2, y2, track_id, ...] that the
@@ -122,12 +129,18 @@ class FrameStore:
                         cameras' 2048x1536 stays a few hundred MB on disk
     """
 
-    def __init__(self, directory):
+    def __init__(self, directory, decoder=None, device=0):
         self.filename = str(directory)
         meta = os.path.join(directory, "metadata.yaml")
         if not os.path.exists(meta):
             raise FileNotFoundError(meta)
-        self.frames = np.load(os.path.join(directory, "frames.npy"), mmap_mode="r")
+        self.format = _store_format(meta)
+        if self.format == "mjpeg":
+            self.frames = MjpegFrames(os.path.join(directory, "frames.avi"), decoder=decoder, device=device)
+        elif self.format == "npy":
+            self.frames = np.load(os.path.join(directory, "frames.npy"), mmap_mode="r")
+        else:
+            raise ValueError(f"{directory}: unknown store format {self.format!r}")
         self.frame_time = np.load(os.path.join(directory, "frame_time.npy"))
         self.frame_number = np.load(os.path.join(directory, "frame_number.npy"))
         with open(os.path.join(directory, "tracks.json")) as f:
@@ -159,6 +172,130 @@ class FrameStore:
 
     def id_preds_of(self, frame_number):
         return None if self.id_preds is None else self.id_preds[self.index_of(frame_number)]
+
+
+def _store_format(meta_path):
+    import yaml
+    with open(meta_path) as f:
+        meta = yaml.safe_load(f) or {}
+    return str((meta.get("__store") or {}).get("format", "npy"))
+
+
+def _gpu_decoder(device=0):
+    from .mjpeg import JpegDecoder
+    return JpegDecoder(device=device)
+
+
+def _gpu_encoder(height, width, quality=90, restart_interval=16, device=0):
+    from .mjpeg import JpegEncoder
+    return JpegEncoder(height, width, quality=quality, restart_interval=restart_interval, device=device)
+
+
+class MjpegFrames:
+    """The image pool of a ``format: mjpeg`` store: what ``frames.npy``'s memory map is to an ``npy`` store.
+    ``shape`` (pool, H, W, 3), ``dtype``, ``len()``; ``frames[i]`` decodes image i to a uint8 (H, W, 3) BGR array
+    (a small LRU keeps the last ``cache`` decoded images: step 1 asks for the same image three times);
+    ``device_frames(indices)`` decodes a batch and leaves it on the device.  The decoder is made on first use."""
+
+    dtype = np.dtype(np.uint8)
+
+    def __init__(self, path, decoder=None, device=0, cache=8):
+        from collections import OrderedDict
+        self.readers = [MjpegAviReader(p) for p in mjpeg_avi_files(path)]
+        self._at = [(r, i) for r in self.readers for i in range(len(r))]
+        H, W = self.readers[0].height, self.readers[0].width
+        if any((r.height, r.width) != (H, W) for r in self.readers):
+            raise ValueError(f"{path}: the rollover files differ in frame size")
+        self.shape = (len(self._at), H, W, 3)
+        self.ndim = 4
+        self.device = device
+        self._factory, self._decoder = decoder or _gpu_decoder, None
+        self._cache, self._cache_size = OrderedDict(), max(1, int(cache))
+
+    def __len__(self):
+        return self.shape[0]
+
+    def frame_bytes(self, i):
+        r, k = self._at[int(i)]
+        return r.frame_bytes(k)
+
+    def _dec(self):
+        if self._decoder is None:
+            self._decoder = self._factory(device=self.device)
+        return self._decoder
+
+    def __getitem__(self, i):
+        if not isinstance(i, (int, np.integer)):
+            raise TypeError("an MjpegFrames is indexed by one integer (use device_frames for a batch)")
+        i = int(i)
+        if i < 0:
+            i += len(self)
+        if not 0 <= i < len(self):
+            raise IndexError(i)
+        if i in self._cache:
+            self._cache.move_to_end(i)
+            return self._cache[i]
+        img = np.asarray(self._dec().decode([self.frame_bytes(i)]))[0]
+        if img.shape != self.shape[1:]:
+            raise ValueError(f"frame {i} is {img.shape}, the store is {self.shape[1:]}")
+        img.setflags(write=False)
+        self._cache[i] = img
+        if len(self._cache) > self._cache_size:
+            self._cache.popitem(last=False)
+        return img
+
+    def __iter__(self):
+        return (self[i] for i in range(len(self)))
+
+    def __array__(self, dtype=None, copy=None):
+        out = np.stack([self[i] for i in range(len(self))]) if len(self) else np.zeros(self.shape, np.uint8)
+        return out if dtype is None else out.astype(dtype)
+
+    def device_frames(self, indices, device=None):
+        """uint8 (len(indices), H, W, 3) on the device: only the compressed bytes are uploaded."""
+        if device is not None and device != self.device and self._decoder is not None:
+            self._decoder = None
+        if device is not None:
+            self.device = device
+        return self._dec().decode_device([self.frame_bytes(i) for i in indices])
+
+
+def convert_frame_store(src, dst, quality=90, restart_interval=16, batch=16, encoder=None, device=0,
+                        max_bytes=2 ** 31 - 2 ** 20):
+    """Write the ``format: mjpeg`` store ``dst`` of the ``npy`` store ``src``: the image pool encoded on the GPU
+    (``encoder``: a factory ``(height, width, quality=, restart_interval=, device=)`` of an object with
+    ``JpegEncoder.encode``; tests inject the NumPy encoder) into ``dst/frames.avi`` (rollover files past
+    ``max_bytes``), the times, numbers, tracker rows, ID predictions and frame index copied.  JPEG is lossy: the
+    new store's images are the decoded ones.  Returns (raw bytes, compressed bytes)."""
+    import shutil
+
+    import yaml
+    store = FrameStore(src)
+    if store.format != "npy":
+        raise ValueError(f"{src}: not a format: npy store")
+    if os.path.exists(os.path.join(dst, "metadata.yaml")):
+        raise FileExistsError(os.path.join(dst, "metadata.yaml"))
+    os.makedirs(dst, exist_ok=True)
+    n, H, W = (int(v) for v in store.frames.shape[:3])
+    enc = (encoder or _gpu_encoder)(H, W, quality=quality, restart_interval=restart_interval, device=device)
+    writer = MjpegAviWriter(os.path.join(dst, "frames.avi"), H, W, max_bytes=max_bytes)
+    total = 0
+    for k in range(0, n, max(1, int(batch))):
+        for jpg in enc.encode(np.array(store.frames[k:k + max(1, int(batch))])):      # a writable copy of the map
+            writer.append(jpg)
+            total += len(jpg)
+    writer.close()
+    for name in ("frame_time.npy", "frame_number.npy", "tracks.json", "id_preds.json", "frame_index.npy"):
+        if os.path.exists(os.path.join(src, name)):
+            shutil.copyfile(os.path.join(src, name), os.path.join(dst, name))
+    with open(os.path.join(src, "metadata.yaml")) as f:
+        meta = yaml.safe_load(f) or {}
+    meta.setdefault("__store", {})
+    meta["__store"].update(format="mjpeg", imgshape=[H, W, 3], quality=int(quality),
+                           restart_interval=int(restart_interval))
+    with open(os.path.join(dst, "metadata.yaml"), "w") as f:      # last: its presence makes the directory a store
+        yaml.safe_dump(meta, f)
+    return n * H * W * 3, total
 
 
 def write_frame_store(directory, frames, frame_time, frame_number, tracks, camera_id, id_preds=None,

@@ -859,7 +859,8 @@ def step1_proc2d_custom(data_name, results_root, raw_root, fps=24.0, t_intv=None
     meta_paths = sorted(glob.glob(os.path.join(raw_root, f"{data_name}.*", "metadata.yaml")))
     if not meta_paths:
         raise FileNotFoundError(f'No imgstore metadata for "{data_name}" in {raw_root}')
-    stores = [FrameStore(os.path.dirname(p)) for p in meta_paths]
+    dev_index = int(str(device_str).split(":")[1]) if ":" in str(device_str) else 0
+    stores = [FrameStore(os.path.dirname(p), device=dev_index) for p in meta_paths]   # mjpeg stores decode there
     md0 = stores[0].get_frame_metadata()
     t0 = md0["frame_time"][0]
     if t_intv is None:

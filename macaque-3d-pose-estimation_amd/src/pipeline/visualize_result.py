@@ -39,7 +39,7 @@ def _gpu_encoder(height, width, quality, device):
 
 def proc(data_name, i_cam, config_path, raw_data_dir=None, results_dir_root='./results3D', out_dir='./output',
          device=0, batch=16, step=1, frame_range=None, skeleton=None, mrksize=3, renderer=None, video=None,
-         quality=90, fps=24.0, encoder=None):
+         quality=90, fps=24.0, encoder=None, decoder=None):
     """visualize_result.py:136-254 for camera ``camera_id[i_cam]`` of ``config_path``.
 
     ``step`` / ``frame_range=(start, stop)`` select the rows ``range(start, stop, step)`` of kp3d's frame axis
@@ -51,6 +51,8 @@ def proc(data_name, i_cam, config_path, raw_data_dir=None, results_dir_root='./r
     ``quality`` (the frames are not copied to the host) and writes ``<out>/<data>_<camid>.avi`` at ``fps`` with
     ``<out>/<data>_<camid>.frame_number.npy`` / ``.frame_time.npy`` beside it.  ``encoder``: a factory
     ``(height, width, quality=, device=)`` of an object with ``JpegEncoder.encode`` (tests inject the NumPy encoder).
+    ``decoder``: the ``FrameStore``'s (a ``format: mjpeg`` store decodes on the GPU; with the GPU renderer the
+    decoded batch never leaves the device).
     Returns the written store's directory (or the AVI's path), or None on the early returns."""
     from mqhip import io as mqio
     from mqhip.geometry import CameraGroup
@@ -85,7 +87,7 @@ def proc(data_name, i_cam, config_path, raw_data_dir=None, results_dir_root='./r
     data_name = os.path.basename(os.path.normpath(result_dir))
     mdata = raw_data_dir + '/' + data_name.split('.')[0] + '.' + str(ID[i_cam])
     frame_num = np.load(result_dir + '/' + str(ID[i_cam]) + '/frame_num.npy')
-    store = mqio.FrameStore(mdata)
+    store = mqio.FrameStore(mdata, decoder=decoder, device=device)
     store_frames_set = set(int(f) for f in store.get_frame_metadata()['frame_number'])
 
     X = np.asarray(data['kp3d'], dtype=np.float64)          # (A, F, J, 3)
@@ -118,7 +120,10 @@ def proc(data_name, i_cam, config_path, raw_data_dir=None, results_dir_root='./r
         fns = [fn for _, fn in part]
         pos = [store.index_of(fn) for fn in fns]
         pool, src_index = np.unique(store.frame_index[pos], return_inverse=True)
-        frames = np.stack([np.asarray(store.frames[int(p)]) for p in pool])      # each source image once
+        if store.format == 'mjpeg' and renderer is None:     # decoded on the device: only JPEG bytes are uploaded
+            frames = store.frames.device_frames([int(p) for p in pool], device)
+        else:
+            frames = np.stack([np.asarray(store.frames[int(p)]) for p in pool])      # each source image once
         out = draw.render(frames, 0, X[:, idx].transpose(1, 0, 2, 3), S[:, idx].transpose(1, 0, 2),
                           src_index=src_index.astype(np.int32))
         if video == 'avi':
