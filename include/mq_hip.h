@@ -616,6 +616,52 @@ int mq_overlay_render(mq_ctx* ctx, const double* cams, int n_cams, const int32_t
                       int64_t frame_stride, int n_src, const int32_t* src_index, int height, int width,
                       int32_t* prim_i, double* prim_d, uint8_t* out, void* stream);
 
+/* The labelled overlay: step 3's tracking video (step3_crossframematching.py visualize :1624-1670), where every
+ * live tracklet is an "animal" whose colour is its voted collar ID (:1642-1646) and whose key is written at the
+ * upper left of its skeleton (cv2.putText :1658-1670).  mq_overlay_primitives' arguments plus device tables:
+ *   colour    : int32 (n_img, n_animals) or NULL.  0..3 picks mq_overlay_render's four colours, any other value
+ *               (step 3's Cid = -1) is black; NULL keeps "colour = animal index"
+ *   label_seg : int32 (n_img, n_animals, max_segs, 4) stroke segments x0, y0, x1, y1 relative to the label
+ *               origin, each coordinate in [-8192, 8192] (a label with one outside is not drawn), 16-byte aligned;
+ *               label_n int32 (n_img, n_animals) segments in use (clamped to [0, max_segs]); both may be NULL when
+ *               max_segs is 0 (no labels);  max_segs in [0, 96];  label_t the stroke thickness in [1, 32]
+ *   prim_i    : int32 (n_img, n_animals, n_joints + 2 + n_pairs, 8): mq_overlay_primitives' slots, then the
+ *               label slot [valid, origin x, origin y, 0, x0, y0, x1, y1] (so n_joints + 2 + n_pairs <= 64)
+ * The origin is (int)x_min, (int)y_min, the NaN-ignoring minima of the projected x and y over all
+ * n_joints + 1 slots before any joint is dropped; no label when either minimum is missing or outside
+ * [-1000, 3000], or label_n is 0.  The box is the segments' extent padded by ceil(label_t / 2).  Coverage of a
+ * segment p0 -> p1 at pixel X, in integers (e = p1 - p0, w = X - p0): w.e <= 0: 4|w|^2 <= t^2; w.e >= |e|^2:
+ * 4|X - p1|^2 <= t^2; else 4 (w x e)^2 <= t^2 |e|^2.  The rule and the stroke font that feeds it
+ * (mqhip/overlay.py) are this project's own: cv2's Hershey glyphs and thick-line rasteriser are unpinned. */
+int mq_overlay_primitives_labelled(mq_ctx* ctx, const double* cams, int n_cams, const int32_t* cam_of_img,
+                                   const double* kp3d, const double* score, int n_img, int n_animals, int n_joints,
+                                   const int32_t* pairs, int n_pairs, const int32_t* radius,
+                                   const int32_t* joint_flags, int mrksize, const int32_t* colour,
+                                   const int32_t* label_seg, const int32_t* label_n, int max_segs, int label_t,
+                                   int32_t* prim_i, double* prim_d, void* stream);
+
+/* mq_overlay_primitives_labelled, then the fused copy + draw of mq_overlay_render (visualize :1622, :1656,
+ * :1667-1670).  A label belongs to its animal's layer: over that animal's skeleton, under every higher animal's
+ * skeleton and label.  More than 8 tracklets: render in passes, a pass's output being the next pass's frames. */
+int mq_overlay_render_labelled(mq_ctx* ctx, const double* cams, int n_cams, const int32_t* cam_of_img,
+                               const double* kp3d, const double* score, int n_img, int n_animals, int n_joints,
+                               const int32_t* pairs, int n_pairs, const int32_t* radius, const int32_t* joint_flags,
+                               int mrksize, const uint8_t* frames, int64_t frame_stride, int n_src,
+                               const int32_t* src_index, int height, int width, const int32_t* colour,
+                               const int32_t* label_seg, const int32_t* label_n, int max_segs, int label_t,
+                               int32_t* prim_i, double* prim_d, uint8_t* out, void* stream);
+
+/* Bilinear resize of uint8 BGR images (csrc/resize.hip): cv2.resize(img, [800, 600]) of visualize :1685 and
+ * visualize_result.py :164, :249, after cv2's 8-bit INTER_LINEAR fixed-point scheme.  src (n, H, W, 3) at
+ * src_stride bytes per image, dst (n, h, w, 3) at dst_stride; they must not overlap.  Per axis, with
+ * scale = (double)src / dst: f = (float)((d + 0.5) * scale - 0.5), s = floor(f), f -= s; s < 0: s = 0, f = 0;
+ * s >= src - 1: s = src - 1, f = 0; taps s and min(s + 1, src - 1) with c1 = rint(f * 2048f),
+ * c0 = rint((1f - f) * 2048f) in float32.  R = I[s] * a0 + I[s1] * a1 along x; out =
+ * (((b0 * (R0 >> 4)) >> 16) + ((b1 * (R1 >> 4)) >> 16) + 2) >> 2 along y, saturated to [0, 255].  This is the
+ * project's restatement (tests/track_video_ref.py, equal bit for bit); parity with cv2 itself is unpinned. */
+int mq_resize_bilinear(mq_ctx* ctx, const uint8_t* src, int64_t src_stride, int n, int height, int width,
+                       uint8_t* dst, int64_t dst_stride, int out_height, int out_width, void* stream);
+
 /* Bundle adjustment of the camera rig on marker traces (multicam_toolbox.py optimize_extrinsic :488-636 and
  * optimize_all_camera_params :638-824): a Schur-complement Levenberg-Marquardt with Marquardt scaling that
  * stands in for the reference's least_squares(method='trf', x_scale='jac') call (:611, :776).

@@ -20,6 +20,7 @@
 #include "cmc.hpp"
 #include "geometry.hpp"
 #include "overlay.hpp"
+#include "resize.hpp"
 #include "jpeg.hpp"
 #include "jpeg_dec.hpp"
 #include "detector.hpp"
@@ -1677,6 +1678,93 @@ int mq_overlay_render(mq_ctx* ctx, const double* cams, int C, const int32_t* cam
   if (rc || n_img == 0) return rc;
   K_TRY(mq::overlay_draw(frames, frame_stride, n_src, src_index, n_img, height, width, A, J, P, mrksize, prim_i,
                          prim_d, out, (hipStream_t)stream));
+  return 0;
+}
+
+static int overlay_labels(const char* who, int J, int P, const int32_t* colour, const int32_t* label_seg,
+                          const int32_t* label_n, int S, int label_t, mq::OverlayLabels& lb) {
+  const std::string w(who);
+  if (J + 2 + P > mq::OVL_MAX_PRIMS)
+    return fail(w + ": n_joints + 2 + n_pairs must be <= 64 primitives per animal (the label takes one)", -2);
+  if (S < 0 || S > mq::OVL_MAX_LABEL_SEGS) return fail(w + ": max_segs must be in [0, 96]", -2);
+  if (label_t < 1 || label_t > 32) return fail(w + ": label_t must be in [1, 32]", -2);
+  if (S > 0 && (!label_seg || !label_n)) return fail(w + ": null label table");
+  if ((uintptr_t)label_seg % 16) return fail(w + ": label_seg must be 16-byte aligned", -2);
+  lb.colour = colour;
+  lb.seg = S > 0 ? label_seg : nullptr;
+  lb.n = S > 0 ? label_n : nullptr;
+  lb.S = S;
+  lb.t = label_t;
+  return 0;
+}
+
+int mq_overlay_primitives_labelled(mq_ctx* ctx, const double* cams, int C, const int32_t* cam_of_img,
+                                   const double* kp3d, const double* score, int n_img, int A, int J,
+                                   const int32_t* pairs, int P, const int32_t* radius, const int32_t* joint_flags,
+                                   int mrksize, const int32_t* colour, const int32_t* label_seg,
+                                   const int32_t* label_n, int S, int label_t, int32_t* prim_i, double* prim_d,
+                                   void* stream) {
+  int rc = check_geo(ctx, cams, C, n_img);
+  if (rc) return rc;
+  mq::OverlaySkeleton sk;
+  mq::OverlayLabels lb;
+  const char* who = "mq_overlay_primitives_labelled";
+  if ((rc = overlay_skeleton(who, A, J, pairs, P, radius, joint_flags, mrksize, sk))) return rc;
+  if ((rc = overlay_labels(who, J, P, colour, label_seg, label_n, S, label_t, lb))) return rc;
+  if (n_img == 0) return 0;
+  if (n_img > 65535) return fail("mq_overlay_primitives_labelled: at most 65535 images per call", -2);
+  if (!cam_of_img || !kp3d || !score || !prim_i || (P > 0 && !prim_d))
+    return fail("mq_overlay_primitives_labelled: null argument");
+  K_TRY(mq::overlay_primitives_labelled(cams, C, cam_of_img, kp3d, score, n_img, A, J, sk, mrksize, lb, prim_i,
+                                        prim_d, (hipStream_t)stream));
+  return 0;
+}
+
+int mq_overlay_render_labelled(mq_ctx* ctx, const double* cams, int C, const int32_t* cam_of_img, const double* kp3d,
+                               const double* score, int n_img, int A, int J, const int32_t* pairs, int P,
+                               const int32_t* radius, const int32_t* joint_flags, int mrksize, const uint8_t* frames,
+                               int64_t frame_stride, int n_src, const int32_t* src_index, int height, int width,
+                               const int32_t* colour, const int32_t* label_seg, const int32_t* label_n, int S,
+                               int label_t, int32_t* prim_i, double* prim_d, uint8_t* out, void* stream) {
+  if (height <= 0 || width <= 0 || width > (1 << 24) || height > (1 << 24))
+    return fail("mq_overlay_render_labelled: bad image size", -2);
+  const int64_t img_bytes = (int64_t)height * width * 3;
+  if (n_src <= 0 || frame_stride < img_bytes) return fail("mq_overlay_render_labelled: bad frame pool", -2);
+  if (n_img > 0) {
+    if (!frames || !src_index || !out) return fail("mq_overlay_render_labelled: null argument");
+    const uint8_t* f_end = frames + (size_t)(n_src - 1) * (size_t)frame_stride + img_bytes;
+    const uint8_t* o_end = out + (size_t)n_img * (size_t)img_bytes;
+    if (frames < o_end && out < f_end)
+      return fail("mq_overlay_render_labelled: out overlaps frames (no in-place drawing)", -2);
+  }
+  int rc = mq_overlay_primitives_labelled(ctx, cams, C, cam_of_img, kp3d, score, n_img, A, J, pairs, P, radius,
+                                          joint_flags, mrksize, colour, label_seg, label_n, S, label_t, prim_i,
+                                          prim_d, stream);
+  if (rc || n_img == 0) return rc;
+  mq::OverlayLabels lb;
+  if ((rc = overlay_labels("mq_overlay_render_labelled", J, P, colour, label_seg, label_n, S, label_t, lb))) return rc;
+  K_TRY(mq::overlay_draw_labelled(frames, frame_stride, n_src, src_index, n_img, height, width, A, J, P, mrksize, lb,
+                                  prim_i, prim_d, out, (hipStream_t)stream));
+  return 0;
+}
+
+// ----------------------------------------------------------------------------- image resize
+int mq_resize_bilinear(mq_ctx* ctx, const uint8_t* src, int64_t src_stride, int n, int H, int W, uint8_t* dst,
+                       int64_t dst_stride, int h, int w, void* stream) {
+  if (!ctx) return fail("mq_resize_bilinear: null ctx");
+  if (H <= 0 || W <= 0 || h <= 0 || w <= 0 || H > (1 << 24) || W > (1 << 24) || h > (1 << 24) || w > (1 << 24))
+    return fail("mq_resize_bilinear: image sizes must be in [1, 2^24]", -2);
+  if (n < 0 || n > 65535) return fail("mq_resize_bilinear: n must be in [0, 65535]", -2);
+  const int64_t src_bytes = (int64_t)H * W * 3, dst_bytes = (int64_t)h * w * 3;
+  if (src_stride < src_bytes || dst_stride < dst_bytes)
+    return fail("mq_resize_bilinear: a stride is below one image", -2);
+  if (n == 0) return 0;
+  if (!src || !dst) return fail("mq_resize_bilinear: null argument");
+  const uint8_t* s_end = src + (size_t)(n - 1) * (size_t)src_stride + src_bytes;
+  const uint8_t* d_end = dst + (size_t)(n - 1) * (size_t)dst_stride + dst_bytes;
+  if (src < d_end && dst < s_end) return fail("mq_resize_bilinear: dst overlaps src", -2);
+  if (hipSetDevice(ctx->device) != hipSuccess) return fail("hipSetDevice failed", -5);
+  K_TRY(mq::resize_bilinear(src, src_stride, n, H, W, dst, dst_stride, h, w, (hipStream_t)stream));
   return 0;
 }
 

@@ -16,6 +16,14 @@
 //     u = px*ex + py*ey, v = py*ex - px*ey, a2 = d2/4, b2 = m*m/4;  inside iff d2 > 0 and u*u*b2 + v*v*a2 <= a2*b2*d2
 // The pixel takes the colour of the highest animal index with a covering primitive (the reference's painter's
 // order: one colour per animal, animals drawn in index order), else the source pixel.
+//
+// Labelled variant (step3_crossframematching.py visualize :1642-1670: the tracklet's voted collar ID picks the
+// colour, cv2.putText writes its key at the skeleton's upper left): the LBL instantiations of both kernels.  Each
+// animal gets one more slot, the last, holding its label: a list of stroke segments relative to an origin.
+//   label segment p0 -> p1 (origin added), thickness t, integers (int64): e = p1 - p0, w = X - p0;
+//     w.e <= 0: 4|w|^2 <= t^2;  w.e >= |e|^2: 4|X - p1|^2 <= t^2;  else 4 (w x e)^2 <= t^2 |e|^2
+// The label is the animal's highest slot, so it lies over that animal's skeleton and under every higher animal.
+// A colour table (B, A) replaces "colour = animal index": entry 0..3 as animal_colour, anything else black.
 #include "common.hpp"
 #include "camera.hpp"
 #include "dlt_dev.hpp"
@@ -24,15 +32,16 @@
 namespace mq {
 
 // ------------------------------------------------------------------------------------------- primitives
+template <bool LBL>
 __global__ __launch_bounds__(64) void overlay_prims_kernel(
     const double* __restrict__ cams, int C, const int32_t* __restrict__ cam_of_img, const double* __restrict__ kp3d,
     const double* __restrict__ score, int A, int J, OverlaySkeleton sk, int mrksize, int32_t* __restrict__ prim_i,
-    double* __restrict__ prim_d) {
+    double* __restrict__ prim_d, OverlayLabels lb) {
   __shared__ double px[OVL_MAX_PRIMS], py[OVL_MAX_PRIMS];
   __shared__ int ok[OVL_MAX_PRIMS];
   const int b = blockIdx.x / A, a = blockIdx.x % A;
   const int lane = threadIdx.x;
-  const int P = sk.n_pairs, NP = J + 1 + P;
+  const int P = sk.n_pairs, NP = J + 1 + P + (LBL ? 1 : 0);
   const int cam = cam_of_img[b];
   const double* x3 = kp3d + ((size_t)b * A + a) * J * 3;
   const double* sc = score + ((size_t)b * A + a) * J;
@@ -97,6 +106,50 @@ __global__ __launch_bounds__(64) void overlay_prims_kernel(
     d[2] = x2;
     d[3] = y2;
   }
+  if constexpr (LBL) {
+    // the label slot (visualize :1658-1670): origin = the NaN-ignoring minima of u and v over all J + 1 slots,
+    // before clean_kp; box = the segments' extent around it, padded by ceil(t / 2)
+    int n = lb.seg ? lb.n[(size_t)b * A + a] : 0;
+    n = n < 0 ? 0 : (n > lb.S ? lb.S : n);
+    int x0 = INT32_MAX, y0 = INT32_MAX, x1 = INT32_MIN, y1 = INT32_MIN;
+    for (int i = lane; i < n; i += 64) {
+      const int32_t* g = lb.seg + (((size_t)b * A + a) * lb.S + i) * 4;
+      x0 = min(x0, min(g[0], g[2]));
+      y0 = min(y0, min(g[1], g[3]));
+      x1 = max(x1, max(g[0], g[2]));
+      y1 = max(y1, max(g[1], g[3]));
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+      x0 = min(x0, __shfl_xor(x0, o));
+      y0 = min(y0, __shfl_xor(y0, o));
+      x1 = max(x1, __shfl_xor(x1, o));
+      y1 = max(y1, __shfl_xor(y1, o));
+    }
+    if (lane == 0) {
+      double xm = NAN, ym = NAN;
+      for (int j = 0; j <= J; ++j) {
+        const double uj = px[j], vj = py[j];
+        if (uj == uj && !(xm <= uj)) xm = uj;
+        if (vj == vj && !(ym <= vj)) ym = vj;
+      }
+      bool valid = n > 0 && xm == xm && ym == ym;
+      if (valid && (xm > 3000 || xm < -1000 || ym > 3000 || ym < -1000)) valid = false;
+      // beyond +-OVL_MAX_LABEL_COORD, 4 (w x e)^2 could leave int64: such a label is not drawn
+      if (valid && (x0 < -OVL_MAX_LABEL_COORD || y0 < -OVL_MAX_LABEL_COORD || x1 > OVL_MAX_LABEL_COORD ||
+                    y1 > OVL_MAX_LABEL_COORD))
+        valid = false;
+      const int ox = valid ? (int)xm : 0, oy = valid ? (int)ym : 0, pad = (lb.t + 1) / 2;
+      int32_t* o = prim_i + (((size_t)b * A + a) * NP + NP - 1) * 8;
+      o[0] = valid;
+      o[1] = ox;
+      o[2] = oy;
+      o[3] = 0;
+      o[4] = valid ? ox + x0 - pad : 0;
+      o[5] = valid ? oy + y0 - pad : 0;
+      o[6] = valid ? ox + x1 + pad : 0;
+      o[7] = valid ? oy + y1 + pad : 0;
+    }
+  }
 }
 
 // ------------------------------------------------------------------------------------------------- draw
@@ -112,11 +165,13 @@ __device__ __forceinline__ uint32_t animal_colour(int a, int ch) {
 
 // One chunk of one row.  S = (first byte of the chunk) % 3: byte i of the chunk is channel (i + S) % 3 of the
 // chunk's pixel (i + S) / 3, whose column is X0 + (i + S) / 3.
-template <int S, bool VEC>
+template <int S, bool VEC, bool LBL>
 __device__ __forceinline__ void draw_chunk(const uint8_t* __restrict__ srow, uint8_t* __restrict__ orow, int byte0,
                                            int row_bytes, int X0, int Y, int W, const uint16_t* list, int n_list,
                                            const int32_t* __restrict__ pi, const double* __restrict__ pd, int NP,
-                                           int J, int P, double b2) {
+                                           int J, int P, double b2, const int32_t* __restrict__ lseg,
+                                           const int32_t* __restrict__ ln, int LS, int lt,
+                                           const int32_t* __restrict__ clr) {
   uint32_t w[4] = {0, 0, 0, 0};
   if (srow) {
     if (VEC) {
@@ -142,7 +197,38 @@ __device__ __forceinline__ void draw_chunk(const uint8_t* __restrict__ srow, uin
       const int x0 = q[4], y0 = q[5], x1 = q[6], y1 = q[7];
       if (Y < y0 || Y > y1 || X0 + OVL_CHUNK_PIX - 1 < x0 || X0 > x1) continue;
       const int animal = idx / NP, slot = idx - animal * NP;
-      if (slot <= J) {
+      if (LBL && slot == NP - 1) {
+        int n = ln[animal];
+        n = n < 0 ? 0 : (n > LS ? LS : n);
+        const int ox = q[1], oy = q[2], pad = (lt + 1) / 2;
+        const int64_t t2 = (int64_t)lt * lt;
+        const int4* g = reinterpret_cast<const int4*>(lseg) + (size_t)animal * LS;
+        for (int i = 0; i < n; ++i) {
+          const int4 sg = g[i];
+          const int ax = ox + sg.x, ay = oy + sg.y, bx = ox + sg.z, by = oy + sg.w;
+          if (Y < min(ay, by) - pad || Y > max(ay, by) + pad || X0 + OVL_CHUNK_PIX - 1 < min(ax, bx) - pad ||
+              X0 > max(ax, bx) + pad)
+            continue;
+          const int64_t ex = bx - ax, ey = by - ay, ee = ex * ex + ey * ey;
+          const int64_t wy = Y - ay, vy = Y - by;
+#pragma unroll
+          for (int k = 0; k < OVL_CHUNK_PIX; ++k) {
+            if (col[k] >= 0) continue;
+            const int64_t wx = X0 + k - ax, we = wx * ex + wy * ey;
+            bool in;
+            if (we <= 0) {
+              in = 4 * (wx * wx + wy * wy) <= t2;
+            } else if (we >= ee) {
+              const int64_t vx = X0 + k - bx;
+              in = 4 * (vx * vx + vy * vy) <= t2;
+            } else {
+              const int64_t cr = wx * ey - wy * ex;
+              in = 4 * cr * cr <= t2 * ee;
+            }
+            if (in) col[k] = animal;
+          }
+        }
+      } else if (slot <= J) {
         const int cx = q[1], cy = q[2], r = q[3];
         const int dy = Y - cy, lim = r * r + r - dy * dy;
 #pragma unroll
@@ -172,8 +258,10 @@ __device__ __forceinline__ void draw_chunk(const uint8_t* __restrict__ srow, uin
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const int k = (i + S) / 3, ch = (i + S) % 3;
-      if (col[k] >= 0 && X0 + k < W)
-        w[i >> 2] = (w[i >> 2] & ~(0xffu << (8 * (i & 3)))) | (animal_colour(col[k], ch) << (8 * (i & 3)));
+      if (col[k] >= 0 && X0 + k < W) {
+        const int c = (LBL && clr) ? clr[col[k]] : col[k];
+        w[i >> 2] = (w[i >> 2] & ~(0xffu << (8 * (i & 3)))) | (animal_colour(c, ch) << (8 * (i & 3)));
+      }
     }
   }
   if (VEC) {
@@ -185,17 +273,25 @@ __device__ __forceinline__ void draw_chunk(const uint8_t* __restrict__ srow, uin
   }
 }
 
-template <bool VEC>
+template <bool VEC, bool LBL>
 __global__ __launch_bounds__(OVL_THREADS) void overlay_draw_kernel(
     const uint8_t* __restrict__ frames, int64_t frame_stride, int n_src, const int32_t* __restrict__ src_index, int H,
     int W, int A, int J, int P, int mrksize, const int32_t* __restrict__ prim_i, const double* __restrict__ prim_d,
-    uint8_t* __restrict__ out, int tiles_x) {
+    uint8_t* __restrict__ out, int tiles_x, OverlayLabels lb) {
   __shared__ uint16_t list[OVL_MAX_ANIMALS * OVL_MAX_PRIMS];
   __shared__ int n_shared;
   const int b = blockIdx.y;
   const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
   const int row_bytes = 3 * W;
-  const int NP = J + 1 + P, N = A * NP;
+  const int NP = J + 1 + P + (LBL ? 1 : 0), N = A * NP;
+  const int32_t* lseg = nullptr;
+  const int32_t* ln = nullptr;
+  const int32_t* clr = nullptr;
+  if constexpr (LBL) {
+    lseg = lb.seg ? lb.seg + (size_t)b * A * lb.S * 4 : nullptr;
+    ln = lb.seg ? lb.n + (size_t)b * A : nullptr;
+    clr = lb.colour ? lb.colour + (size_t)b * A : nullptr;
+  }
   const int32_t* pi = prim_i + (size_t)b * N * 8;
   const double* pd = prim_d + (size_t)b * A * P * 4;
   const int chunk0 = tx * OVL_TILE_CHUNKS, row0 = ty * OVL_TILE_ROWS;
@@ -236,11 +332,14 @@ __global__ __launch_bounds__(OVL_THREADS) void overlay_draw_kernel(
     const uint8_t* srow = simg ? simg + (size_t)Y * row_bytes : nullptr;
     uint8_t* orow = oimg + (size_t)Y * row_bytes;
     if (S == 0)
-      draw_chunk<0, VEC>(srow, orow, byte0, row_bytes, X0, Y, W, list, n_list, pi, pd, NP, J, P, b2);
+      draw_chunk<0, VEC, LBL>(srow, orow, byte0, row_bytes, X0, Y, W, list, n_list, pi, pd, NP, J, P, b2, lseg, ln,
+                               lb.S, lb.t, clr);
     else if (S == 1)
-      draw_chunk<1, VEC>(srow, orow, byte0, row_bytes, X0, Y, W, list, n_list, pi, pd, NP, J, P, b2);
+      draw_chunk<1, VEC, LBL>(srow, orow, byte0, row_bytes, X0, Y, W, list, n_list, pi, pd, NP, J, P, b2, lseg, ln,
+                               lb.S, lb.t, clr);
     else
-      draw_chunk<2, VEC>(srow, orow, byte0, row_bytes, X0, Y, W, list, n_list, pi, pd, NP, J, P, b2);
+      draw_chunk<2, VEC, LBL>(srow, orow, byte0, row_bytes, X0, Y, W, list, n_list, pi, pd, NP, J, P, b2, lseg, ln,
+                               lb.S, lb.t, clr);
   }
 }
 
@@ -250,8 +349,19 @@ int overlay_primitives(const double* cams, int C, const int32_t* cam_of_img, con
                        hipStream_t s) {
   if (B <= 0 || A <= 0) return 0;
   if (A > OVL_MAX_ANIMALS || J < 7 || sk.n_pairs < 0 || J + 1 + sk.n_pairs > OVL_MAX_PRIMS) return -2;
-  hipLaunchKernelGGL(overlay_prims_kernel, dim3(B * A), dim3(64), 0, s, cams, C, cam_of_img, kp3d, score, A, J, sk,
-                     mrksize, prim_i, prim_d);
+  hipLaunchKernelGGL(overlay_prims_kernel<false>, dim3(B * A), dim3(64), 0, s, cams, C, cam_of_img, kp3d, score, A, J,
+                     sk, mrksize, prim_i, prim_d, OverlayLabels{});
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int overlay_primitives_labelled(const double* cams, int C, const int32_t* cam_of_img, const double* kp3d,
+                                const double* score, int B, int A, int J, const OverlaySkeleton& sk, int mrksize,
+                                const OverlayLabels& lb, int32_t* prim_i, double* prim_d, hipStream_t s) {
+  if (B <= 0 || A <= 0) return 0;
+  if (A > OVL_MAX_ANIMALS || J < 7 || sk.n_pairs < 0 || J + 2 + sk.n_pairs > OVL_MAX_PRIMS) return -2;
+  if (lb.S < 0 || lb.S > OVL_MAX_LABEL_SEGS || lb.t < 1 || lb.t > 32 || (lb.seg && !lb.n)) return -2;
+  hipLaunchKernelGGL(overlay_prims_kernel<true>, dim3(B * A), dim3(64), 0, s, cams, C, cam_of_img, kp3d, score, A, J,
+                     sk, mrksize, prim_i, prim_d, lb);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -268,11 +378,32 @@ int overlay_draw(const uint8_t* frames, int64_t frame_stride, int n_src, const i
                    (uintptr_t)out % 16 == 0;
   const dim3 grid(tiles_x * tiles_y, B);
   if (vec)
-    hipLaunchKernelGGL(overlay_draw_kernel<true>, grid, dim3(OVL_THREADS), 0, s, frames, frame_stride, n_src, src_index,
-                       H, W, A, J, P, mrksize, prim_i, prim_d, out, tiles_x);
+    hipLaunchKernelGGL((overlay_draw_kernel<true, false>), grid, dim3(OVL_THREADS), 0, s, frames, frame_stride, n_src,
+                       src_index, H, W, A, J, P, mrksize, prim_i, prim_d, out, tiles_x, OverlayLabels{});
   else
-    hipLaunchKernelGGL(overlay_draw_kernel<false>, grid, dim3(OVL_THREADS), 0, s, frames, frame_stride, n_src,
-                       src_index, H, W, A, J, P, mrksize, prim_i, prim_d, out, tiles_x);
+    hipLaunchKernelGGL((overlay_draw_kernel<false, false>), grid, dim3(OVL_THREADS), 0, s, frames, frame_stride, n_src,
+                       src_index, H, W, A, J, P, mrksize, prim_i, prim_d, out, tiles_x, OverlayLabels{});
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int overlay_draw_labelled(const uint8_t* frames, int64_t frame_stride, int n_src, const int32_t* src_index, int B,
+                          int H, int W, int A, int J, int P, int mrksize, const OverlayLabels& lb,
+                          const int32_t* prim_i, const double* prim_d, uint8_t* out, hipStream_t s) {
+  if (B <= 0 || H <= 0 || W <= 0) return 0;
+  if (A < 0 || A > OVL_MAX_ANIMALS || J + 2 + P > OVL_MAX_PRIMS || B > 65535) return -2;
+  if (lb.S < 0 || lb.S > OVL_MAX_LABEL_SEGS || lb.t < 1 || lb.t > 32 || (lb.seg && !lb.n)) return -2;
+  const int row_bytes = 3 * W;
+  const int tiles_x = (row_bytes + 16 * OVL_TILE_CHUNKS - 1) / (16 * OVL_TILE_CHUNKS);
+  const int tiles_y = (H + OVL_TILE_ROWS - 1) / OVL_TILE_ROWS;
+  const bool vec = row_bytes % 16 == 0 && frame_stride % 16 == 0 && (uintptr_t)frames % 16 == 0 &&
+                   (uintptr_t)out % 16 == 0;
+  const dim3 grid(tiles_x * tiles_y, B);
+  if (vec)
+    hipLaunchKernelGGL((overlay_draw_kernel<true, true>), grid, dim3(OVL_THREADS), 0, s, frames, frame_stride, n_src,
+                       src_index, H, W, A, J, P, mrksize, prim_i, prim_d, out, tiles_x, lb);
+  else
+    hipLaunchKernelGGL((overlay_draw_kernel<false, true>), grid, dim3(OVL_THREADS), 0, s, frames, frame_stride, n_src,
+                       src_index, H, W, A, J, P, mrksize, prim_i, prim_d, out, tiles_x, lb);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

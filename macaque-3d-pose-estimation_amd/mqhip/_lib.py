@@ -28,6 +28,7 @@ EXPORTED = [
     "mq_cmc_create", "mq_cmc_destroy", "mq_cmc_reset", "mq_cmc_apply",
     "mq_tracklet_traces", "mq_tracklet_id_votes",
     "mq_overlay_primitives", "mq_overlay_render",
+    "mq_overlay_primitives_labelled", "mq_overlay_render_labelled", "mq_resize_bilinear",
     "mq_bundle_adjust",
     "mq_jpeg_encode", "mq_jpeg_parse", "mq_jpeg_decode",
     "mq_decode_udp_topk", "mq_viterbi_filter_multi", "mq_triangulate_possible",
@@ -120,6 +121,11 @@ _SIGS = {
     "mq_overlay_primitives": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, i32, vp, vp, vp]),
     "mq_overlay_render": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, i32, vp, i64, i32, vp, i32, i32,
                                 vp, vp, vp, vp]),
+    "mq_overlay_primitives_labelled": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, i32, vp, vp, vp,
+                                             i32, i32, vp, vp, vp]),
+    "mq_overlay_render_labelled": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, i32, vp, i64, i32, vp,
+                                         i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
+    "mq_resize_bilinear": (i32, [vp, vp, i64, i32, i32, i32, vp, i64, i32, i32, vp]),
     "mq_jpeg_max_bytes": (C.c_size_t, [i32, i32, i32]),     # size_t: not in EXPORTED (the int / char* entry points)
     "mq_jpeg_encode": (i32, [vp, vp, i64, i32, i32, i32, i32, i32, vp, i64, vp, vp]),
     "mq_jpeg_parse": (i32, [vp, i64, vp]),                  # host only: no device call

@@ -44,7 +44,7 @@ from src.pipeline import step4_aniposefiltering as step4
 def proc(data_name, fps, results_dir_root, device_str, config_path, raw_data_dir, n_kp, vidfile_prefix='',
          n_animal=4, track_to_animal=None, pose_model=None, id_model="auto", world=1, rank=0, group=None,
          sharded=False, gather_device=None, timings=None, association="known", visualize=None,
-         out_dir='./output', visualize_video=None, video_quality=90):
+         out_dir='./output', visualize_video=None, video_quality=90, step3_video=None, video_size=None):
     """run_demo.py:21-30: step 1 -> (known assignment) -> step 4; returns step 4's kp3d dict (on rank 0;
     None on the other ranks of a sharded run).  ``timings``: optional dict filled with wall seconds per
     stage.
@@ -57,7 +57,13 @@ def proc(data_name, fps, results_dir_root, device_str, config_path, raw_data_dir
     ``visualize``: None (default: nothing is rendered, no output directory is made), "all" (every camera of
     ``camera_id``, as run_demo.py:33-39) or a list of camera indices; rank 0 renders them after step 4 into
     ``out_dir`` (``src.pipeline.visualize_result.proc``); ``visualize_video="avi"`` makes them Motion-JPEG AVI
-    files at JPEG quality ``video_quality`` and ``fps`` instead of frame stores.
+    files at JPEG quality ``video_quality`` and ``fps`` instead of frame stores.  ``video_size=(width, height)``
+    resizes the rendered frames on the GPU before they are encoded or stored (the reference's 800 x 600).
+
+    ``step3_video``: a camera index; with ``association="match"`` step 3 also writes its tracking video
+    (``step3.visualize``: every third frame, the live tracklets' skeletons in their voted ID colours with their
+    keys) to ``vidfile_prefix + '<camid>.avi'`` (default prefix ``<out_dir>/<data>_track_``) at ``video_size``
+    (default 800 x 600).
 
     Steps 3-4 take step 1's rows in memory (the files are still written, by a background thread joined
     before returning).  On a sharded run (``world`` > 1 or ``sharded``) rank r post-processes and writes
@@ -75,6 +81,8 @@ def proc(data_name, fps, results_dir_root, device_str, config_path, raw_data_dir
     t1 = time.perf_counter()
     if association not in ("known", "match"):
         raise ValueError(f"association must be 'known' or 'match', got {association!r}")
+    if step3_video is not None and association != "match":
+        raise ValueError("step3_video needs association='match': the known assignment builds no tracklets")
     try:
         kp2d = None if association == "match" else step3.kp2d_from_step1(
             s1out, step3.camera_ids(config_path), n_animal=n_animal, n_kp=n_kp,
@@ -102,8 +110,12 @@ def proc(data_name, fps, results_dir_root, device_str, config_path, raw_data_dir
             if association == "match":
                 from mqhip import io as mqio
                 step2.proc(data_name, results_dir_root, raw_data_dir, config_path, device=device)
+                vid = {} if step3_video is None else dict(
+                    save_vid=True, save_vid_cam=int(step3_video), fps=float(fps), quality=video_quality,
+                    size=(800, 600) if video_size is None else tuple(video_size),
+                    vidfile_prefix=vidfile_prefix or os.path.join(out_dir, data_name + '_track_'))
                 step3.proc(data_name, results_dir_root, raw_data_dir, config_path, n_animal=n_animal, n_kp=n_kp,
-                           device=device)
+                           device=device, **vid)
                 kp2d = mqio.load_array_pickle(os.path.join(result_dir, "kp2d.pickle"))
             else:
                 kp2d = step3.proc_known_assignment(data_name, results_dir_root, config_path, n_animal=n_animal,
@@ -123,7 +135,7 @@ def proc(data_name, fps, results_dir_root, device_str, config_path, raw_data_dir
                 _barrier(group)            # ... of the rank that owns the camera: every rank has joined its writer
         if visualize is not None and rank == 0:
             _visualize(visualize, data_name, config_path, raw_data_dir, results_dir_root, out_dir, device,
-                       visualize_video, video_quality, fps)
+                       visualize_video, video_quality, fps, video_size)
     finally:
         if s1out is not None:
             s1out.wait()
@@ -137,7 +149,7 @@ def proc(data_name, fps, results_dir_root, device_str, config_path, raw_data_dir
 
 
 def _visualize(visualize, data_name, config_path, raw_data_dir, results_dir_root, out_dir, device, video=None,
-               quality=90, fps=24.0):
+               quality=90, fps=24.0, size=None):
     """run_demo.py:33-39: one ``vis.proc`` per camera (every camera of ``camera_id`` for "all")."""
     import yaml
     from src.pipeline import visualize_result as vis
@@ -147,7 +159,7 @@ def _visualize(visualize, data_name, config_path, raw_data_dir, results_dir_root
     for i_cam in cams:
         print(f"[INFO] Generating overlay frames for camera {ID[i_cam]} (index {i_cam}) ...")
         vis.proc(data_name, i_cam, config_path, raw_data_dir, results_dir_root=results_dir_root, out_dir=out_dir,
-                 device=device, video=video, quality=quality, fps=float(fps))
+                 device=device, video=video, quality=quality, fps=float(fps), size=size)
 
 
 def _barrier(group):
@@ -201,13 +213,20 @@ if __name__ == '__main__':
     ap.add_argument("--video", choices=("avi",), default=None,
                     help="avi: --visualize writes Motion-JPEG <data>_<camid>.avi files instead of frame stores")
     ap.add_argument("--video-quality", type=int, default=90, help="JPEG quality of --video avi, 1..100")
+    ap.add_argument("--step3-video", type=int, default=None, metavar="N",
+                    help="with --association match: step 3's tracking video of camera index N (Motion-JPEG AVI)")
+    ap.add_argument("--video-size", default=None, metavar="WxH",
+                    help="resize rendered frames to W x H on the GPU (--step3-video defaults to 800x600)")
     a = ap.parse_args()
+    size_arg = None if a.video_size is None else tuple(int(v) for v in a.video_size.lower().split("x"))
+    if size_arg is not None and (len(size_arg) != 2 or min(size_arg) < 1):
+        ap.error("--video-size must be WxH, e.g. 800x600")
     vis_arg = None if a.visualize is None else ("all" if a.visualize == "all" else
                                                 [int(i) for i in a.visualize.split(",")])
     W, R, L, G, dev = _dist_from_env()
     proc(a.data, a.fps, a.results, f"cuda:{L}", a.config, a.raw, a.n_kp, world=W, rank=R, group=G,
          gather_device=dev, association=a.association, visualize=vis_arg, out_dir=a.out,
-         visualize_video=a.video, video_quality=a.video_quality)
+         visualize_video=a.video, video_quality=a.video_quality, step3_video=a.step3_video, video_size=size_arg)
     if W > 1:
         import torch.distributed as dist
         dist.barrier()

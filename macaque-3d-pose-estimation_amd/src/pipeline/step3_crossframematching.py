@@ -8,7 +8,8 @@ seen, written by ``create_kp2dfile`` (step3:872-915).  This module has both ways
 * the association itself, under the reference's names (second half of the file): ``proc`` / ``main_proc``
   and their stages, with the per-cell 3D lift and the ID votes on the GPU (``mqhip.tracklets``:
   ``mq_tracklet_traces`` / ``mq_tracklet_id_votes``) and the combinatorial part on the host;
-  ``run_demo.proc(association="match")`` runs it after step 2;
+  ``run_demo.proc(association="match")`` runs it after step 2; ``visualize`` (``proc(save_vid=True)``) is its
+  tracking video, drawn, resized and encoded on the GPU;
 * the writer fed from a KNOWN track -> individual assignment instead (the benchmark's "association
   bypassed" path, SURVEY 8(d), and ``run_demo.proc``'s default):
 
@@ -1035,10 +1036,139 @@ def main_proc(config_path, result_dir, rmse_thr=200.0, camparam=None, device=0, 
     return Trk, Cid, T
 
 
+def _gpu_renderer(cgroup, height, width, skeleton, mrksize, device):
+    from mqhip.overlay import OverlayRenderer
+    return OverlayRenderer(cgroup, height, width, skeleton=skeleton, mrksize=mrksize, device=device)
+
+
+def _gpu_encoder(height, width, quality, device):
+    from mqhip.mjpeg import JpegEncoder
+    return JpegEncoder(height, width, quality=quality, device=device)
+
+
+def _gpu_resizer(frames, height, width, device=0):
+    from mqhip.resize import resize_bilinear
+    return resize_bilinear(frames, height, width, device=device)
+
+
+VIS_MAX_TRACKLETS = 8    # mqhip.overlay.MAX_ANIMALS: tracklets of one frame drawn per render pass
+
+
+def visualize(vis_cam, config_path, result_dir, raw_data_dir, T=None, vidfile_prefix='', size=(800, 600), step=3,
+              fps=24.0, quality=90, batch=16, device=0, camparam=None, renderer=None, encoder=None, resizer=None,
+              lift=None, decoder=None):
+    """step3:1570-1688: the tracking video of camera ``camera_id[vis_cam]``.  Every ``step``-th frame of
+    track.pickle's range, each live tracklet (any box id >= 0 in the frame) lifted from its 2D rows, reprojected
+    and drawn as a skeleton in the colour of its voted collar ID (collar_id.pickle; -1 is black) with its key
+    written at the upper left (:1658-1670); the picture is then resized to ``size`` = (width, height) (:1685;
+    None keeps the camera's size), encoded as JPEG at ``quality`` and appended to the Motion-JPEG AVI
+    ``vidfile_prefix + '<camid>.avi'`` at ``fps`` (where the reference writes an mp4 through cv2), with
+    ``.frame_number.npy`` / ``.frame_time.npy`` beside it.  Lift, drawing, resize and encoding run on the GPU
+    (``mq_tracklet_traces``, ``mq_overlay_render_labelled``, ``mq_resize_bilinear``, ``mq_jpeg_encode``): one lift
+    launch per ``batch`` frames, and only the lifted joints (which the renderer takes as host arrays) and the JPEG
+    bytes leave the device.
+
+    ``T``: the rows main_proc returned (``proc`` passes them; they carry step 3's renumbered box ids); None reads
+    the cameras' alldata.json as the reference does.  A frame with more than 8 live tracklets is drawn in passes
+    of 8 in ``Trk``'s key order, a pass's output being the next pass's source, which keeps the painter's order.
+    The scores handed to the renderer are 1, as the reference's constant score column (:1652): the renderer's
+    "no joint with X != 0 and score > 0" gate could then only drop a tracklet whose 18 lifted X coordinates are
+    all exactly 0.0, which the lift cannot return for a cell it triangulated (an absent joint is NaN, and
+    NaN != 0), so no tracklet is nulled by it.  A frame number absent from the store is skipped with a warning.
+    ``renderer`` / ``encoder`` / ``decoder`` as in ``visualize_result.proc``; ``resizer``: a callable
+    ``(frames, height, width, device=)``; ``lift``: a factory ``(rows)`` of an object with
+    ``TrackletLift.traces`` (tests inject the NumPy restatements).  Returns the AVI's path, or None (and writes
+    nothing) when track.pickle holds no tracklet."""
+    cam_ids = camera_ids(config_path)
+    with open(config_path, 'r') as f:
+        ID = yaml.safe_load(f)['camera_id']
+    if camparam is None:
+        calib = os.path.join(os.path.dirname(config_path), "calibration.toml")
+        if not os.path.exists(calib):
+            calib = os.path.join(result_dir, "calibration.toml")
+        camparam = get_camparam(config_path, calibration_path=calib)
+    from mqhip.association import StepTwoCameras
+    cams = camparam if isinstance(camparam, StepTwoCameras) else StepTwoCameras(camparam, device=device)
+    if T is None:
+        T = load_alldata(result_dir, cam_ids)
+    Trk = mqio.load_array_pickle(os.path.join(result_dir, 'track.pickle'))
+    Cid = mqio.load_array_pickle(os.path.join(result_dir, 'collar_id.pickle'))
+    vid_path = vidfile_prefix + '{:d}.avi'.format(ID[vis_cam])
+    keys = list(Trk.keys())
+    if not keys:        # the reference takes the frame count from the first tracklet and fails without one
+        print('no tracklets:', result_dir)
+        return None
+
+    data_name = os.path.basename(os.path.normpath(result_dir)).split('.')[0]
+    store = mqio.FrameStore(raw_data_dir + '/' + data_name + '.' + str(ID[vis_cam]), decoder=decoder, device=device)
+    frame_num = np.load(result_dir + '/' + str(ID[vis_cam]) + '/frame_num.npy')
+    have = set(int(f) for f in store.get_frame_metadata()['frame_number'])
+    n_frame = Trk[keys[0]].shape[0]
+    rows = []
+    for i_frame in range(0, min(n_frame, len(frame_num)), max(1, int(step))):
+        fn = int(frame_num[i_frame])
+        if fn not in have:
+            print(f'[warning] Skipping frame {fn}: not found in the frame store')
+            continue
+        rows.append((i_frame, fn))
+
+    H, W = (int(v) for v in store.frames.shape[1:3])
+    w_out, h_out = (W, H) if size is None else (int(size[0]), int(size[1]))
+    draw = (renderer or _gpu_renderer)(cams.proj.subset_cameras([vis_cam]), H, W, "v1", 3, device)
+    resize = resizer or _gpu_resizer
+    encode = (encoder or _gpu_encoder)(h_out, w_out, quality=quality, device=device)
+    tracer = (lift(T) if lift is not None else None)
+    if tracer is None:
+        from mqhip.tracklets import TrackletLift
+        tracer = TrackletLift(cams, T, device)
+    writer = mqio.MjpegAviWriter(vid_path, h_out, w_out, fps=fps)
+    n_kp = 17
+    batch = max(1, int(batch))
+    for k0 in range(0, len(rows), batch):
+        part = rows[k0:k0 + batch]
+        fns = [fn for _, fn in part]
+        pos = [store.index_of(fn) for fn in fns]
+        pool, src_index = np.unique(store.frame_index[pos], return_inverse=True)
+        if store.format == 'mjpeg' and renderer is None:     # decoded on the device: only JPEG bytes are uploaded
+            out = store.frames.device_frames([int(p) for p in pool], device)
+        else:
+            out = np.stack([np.asarray(store.frames[int(p)]) for p in pool])      # each source image once
+        src_index = src_index.astype(np.int32)
+        live = [[i for i, k in enumerate(keys) if np.any(Trk[k][i_frame] >= 0)] for i_frame, _ in part]
+        cells = np.array([[i, i_frame] for (i_frame, _), ks in zip(part, live) for i in ks], dtype=np.int32)
+        p3d = tracer.traces(Trk, cells=cells.reshape(-1, 2), return_p3d=True)[2] if len(cells) else None
+        first = np.concatenate([[0], np.cumsum([len(ks) for ks in live])])
+        B = len(part)
+        n_max = max(len(ks) for ks in live)
+        for p0 in range(0, max(n_max, 1), VIS_MAX_TRACKLETS):
+            A = max(1, min(VIS_MAX_TRACKLETS, n_max - p0))
+            kp3d = np.full((B, A, n_kp, 3), np.nan)
+            colour = np.full((B, A), -1, dtype=np.int32)
+            labels = [[None] * A for _ in range(B)]
+            for b, ((i_frame, _), ks) in enumerate(zip(part, live)):
+                for a, i in enumerate(ks[p0:p0 + A]):
+                    kp3d[b, a] = p3d[first[b] + p0 + a]
+                    colour[b, a] = int(Cid[keys[i]][i_frame])
+                    labels[b][a] = str(keys[i])
+            out = draw.render(out, 0, kp3d, np.ones((B, A, n_kp)), src_index=src_index, colour=colour, labels=labels,
+                              label_scale=2.0, label_thickness=5)
+            src_index = np.arange(B, dtype=np.int32)
+        if (h_out, w_out) != (H, W):
+            out = resize(out, h_out, w_out, device=device)
+        for jpg, fn, t in zip(encode.encode(out), fns, store.frame_time[pos]):
+            writer.append(jpg, fn, t)
+    writer.close()
+    return vid_path
+
+
 def proc(data_name, result_dir_root, raw_data_dir, config_path, save_vid=False, save_vid_cam=2, rmse_thr=200.0,
-         vidfile_prefix='', n_animal=4, n_kp=17, device=0):
-    """step3:30-34.  Rendering (``save_vid``) is out of scope."""
+         vidfile_prefix='', n_animal=4, n_kp=17, device=0, **vis_kw):
+    """step3:30-34.  ``save_vid``: ``visualize`` for camera ``save_vid_cam`` on the rows main_proc returned;
+    ``vis_kw`` are ``visualize``'s keyword options."""
+    result_dir = result_dir_root + '/' + data_name
+    Trk, Cid, T = main_proc(config_path, result_dir, rmse_thr=rmse_thr, device=device, n_animal=n_animal, n_kp=n_kp,
+                            camparam=vis_kw.get('camparam'))
     if save_vid:
-        raise NotImplementedError("save_vid: drawing is out of scope on MI355X")
-    return main_proc(config_path, result_dir_root + '/' + data_name, rmse_thr=rmse_thr, device=device,
-                     n_animal=n_animal, n_kp=n_kp)
+        visualize(save_vid_cam, config_path, result_dir, raw_data_dir, T=T, vidfile_prefix=vidfile_prefix,
+                  device=device, **vis_kw)
+    return Trk, Cid, T

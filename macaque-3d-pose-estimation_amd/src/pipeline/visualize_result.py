@@ -37,9 +37,14 @@ def _gpu_encoder(height, width, quality, device):
     return JpegEncoder(height, width, quality=quality, device=device)
 
 
+def _gpu_resizer(frames, height, width, device=0):
+    from mqhip.resize import resize_bilinear
+    return resize_bilinear(frames, height, width, device=device)
+
+
 def proc(data_name, i_cam, config_path, raw_data_dir=None, results_dir_root='./results3D', out_dir='./output',
          device=0, batch=16, step=1, frame_range=None, skeleton=None, mrksize=3, renderer=None, video=None,
-         quality=90, fps=24.0, encoder=None, decoder=None):
+         quality=90, fps=24.0, encoder=None, decoder=None, size=None, resizer=None):
     """visualize_result.py:136-254 for camera ``camera_id[i_cam]`` of ``config_path``.
 
     ``step`` / ``frame_range=(start, stop)`` select the rows ``range(start, stop, step)`` of kp3d's frame axis
@@ -53,6 +58,9 @@ def proc(data_name, i_cam, config_path, raw_data_dir=None, results_dir_root='./r
     ``(height, width, quality=, device=)`` of an object with ``JpegEncoder.encode`` (tests inject the NumPy encoder).
     ``decoder``: the ``FrameStore``'s (a ``format: mjpeg`` store decodes on the GPU; with the GPU renderer the
     decoded batch never leaves the device).
+    ``size``: None (default) keeps the camera's size; ``(width, height)`` resizes every rendered batch on the device
+    before it is encoded or stored (``mqhip.resize.resize_bilinear``: the reference's cv2.resize to 800 x 600,
+    :164, :249).  ``resizer``: a callable ``(frames, height, width, device=)`` in its place (tests inject NumPy).
     Returns the written store's directory (or the AVI's path), or None on the early returns."""
     from mqhip import io as mqio
     from mqhip.geometry import CameraGroup
@@ -108,11 +116,12 @@ def proc(data_name, i_cam, config_path, raw_data_dir=None, results_dir_root='./r
     H, W = (int(v) for v in store.frames.shape[1:3])
     cgroup = CameraGroup.load(result_dir + '/calibration.toml', device=device).subset_cameras_names([str(ID[i_cam])])
     draw = (renderer or _gpu_renderer)(cgroup, H, W, skeleton, mrksize, device)
+    w_out, h_out = (W, H) if size is None else (int(size[0]), int(size[1]))
     if video == 'avi':
-        encode = (encoder or _gpu_encoder)(H, W, quality=quality, device=device)
-        writer = mqio.MjpegAviWriter(vid_path, H, W, fps=fps)
+        encode = (encoder or _gpu_encoder)(h_out, w_out, quality=quality, device=device)
+        writer = mqio.MjpegAviWriter(vid_path, h_out, w_out, fps=fps)
     else:
-        writer = mqio.FrameStoreWriter(vid_path, len(rows), H, W, ID[i_cam])
+        writer = mqio.FrameStoreWriter(vid_path, len(rows), h_out, w_out, ID[i_cam])
     batch = max(1, int(batch))
     for k in range(0, len(rows), batch):
         part = rows[k:k + batch]
@@ -126,6 +135,8 @@ def proc(data_name, i_cam, config_path, raw_data_dir=None, results_dir_root='./r
             frames = np.stack([np.asarray(store.frames[int(p)]) for p in pool])      # each source image once
         out = draw.render(frames, 0, X[:, idx].transpose(1, 0, 2, 3), S[:, idx].transpose(1, 0, 2),
                           src_index=src_index.astype(np.int32))
+        if size is not None:
+            out = (resizer or _gpu_resizer)(out, h_out, w_out, device=device)
         if video == 'avi':
             for jpg, fn, t in zip(encode.encode(out), fns, store.frame_time[pos]):
                 writer.append(jpg, fn, t)
