@@ -523,6 +523,36 @@ int mq_optim_points(mq_ctx* ctx, const double* cams, int n_cams, const double* p
                     double reproj_error_threshold, int reproj_loss, int n_deriv_smooth, int fix_lengths,
                     int max_iter, double ftol, int solver, double* stats, void* stream);
 
+/* CameraGroup.optim_points_possible (cameras.py:1417-1513; residuals _error_fun_triangulation_possible :1622-1667,
+ * initialisation _initialize_params_triangulation_possible :1699-1712, pattern
+ * _jac_sparsity_triangulation_possible :1795-1847) for B animals at once: optim_points' residuals on a soft 2D point
+ * per (camera, frame, joint) cell -- the softmax (beta 5) over one variable per candidate -- plus one row
+ * 10 (1 - std(softmax over all n_possible slots)) per cell with a finite candidate.  Replaces scipy least_squares
+ * (:1473-1488: trf, 2-point sparse Jacobian, loss 'linear', ftol 1e-3) by the same algorithm on the analytic
+ * Jacobian, as mq_optim_points solver 0 (csrc/optim_possible.hip).  Added within ABI 8.
+ *   p2d  device (B, C, F, J, n_possible, 2) float64, NaN = absent candidate (any NaN pattern)
+ *   x    device (B, F*J*3 + n_strong + n_weak) in/out: [p3d, strong lengths, weak lengths]; the alphas start
+ *        at 0 and stay inside the library
+ *   alphas_norm  device (B, C, F, J, n_possible) out: the softmax weights, NaN at NaN candidates
+ *   cams device (n_cams, 24) float64 camera rows (layout at the top of this file)
+ *   constraints host int32 (n_strong + n_weak, 2) joint pairs; scale_smooth_full host (B) float64
+ *   reproj_loss 0 linear, 1 soft_l1 (reference default), 2 huber
+ *   max_nfev 0 = scipy's default, 100 x parameters (3D points, lengths and one alpha per finite candidate)
+ *   stats host (B, 8) float64 out: initial cost, final cost, iterations, scipy's status (0 max_nfev, 1 gtol, 2 ftol,
+ *         3 xtol, 4 ftol + xtol), nfev, njev, lsmr iterations in total, the longest lsmr run
+ *   stream the HIP stream (hipStream_t) the work is queued on; the call returns after it has finished
+ *   solver must be 0; n_possible in [1, 4]; n_frames > n_deriv_smooth; 1 <= n_cams <= 16; n_joints <= 32;
+ *   n_strong + n_weak <= 64; n_deriv_smooth in 1..3.  Errors (-2 and mq_last_error) are raised before anything
+ *   is launched.
+ * A workgroup per block of 4 frames of one animal; an animal's result depends, bit for bit, only on its own
+ * problem (not on the batch or the device). */
+int mq_optim_points_possible(mq_ctx* ctx, const double* cams, int n_cams, const double* p2d, double* x,
+                             double* alphas_norm, int n_animals, int n_frames, int n_joints, int n_possible,
+                             const int32_t* constraints, int n_strong, int n_weak, const double* scale_smooth_full,
+                             double scale_length, double scale_length_weak, double reproj_error_threshold,
+                             int reproj_loss, int n_deriv_smooth, int max_nfev, double ftol, int solver,
+                             double* stats, void* stream);
+
 /* ---- Camera-motion compensation for BoT-SORT (csrc/cmc.hip): boxmot 12.0.7 cmc/sift.py SIFT.apply restated
  * stage by stage, HIP from the uint8 frame to the 2x3 warp.  tests/cmc_ref.py is the numpy restatement the
  * kernels mirror; cv2 parity is unpinned.  All pointers are device pointers unless marked host. */

@@ -1367,6 +1367,40 @@ int mq_optim_points(mq_ctx* ctx, const double* cams, int C, const double* p2d, d
   return 0;
 }
 
+int mq_optim_points_possible(mq_ctx* ctx, const double* cams, int C, const double* p2d, double* x, double* alphas_norm,
+                             int B, int F, int J, int P, const int32_t* constraints, int n_strong, int n_weak,
+                             const double* scale_smooth_full, double scale_length, double scale_length_weak,
+                             double reproj_error_threshold, int reproj_loss, int n_deriv_smooth, int max_nfev,
+                             double ftol, int solver, double* stats, void* stream) {
+  const char* me = "mq_optim_points_possible: ";
+  if (!ctx || !cams || !p2d || !x || !alphas_norm || !scale_smooth_full || !stats)
+    return fail(std::string(me) + "null argument");
+  if (B < 0 || F < 0 || J < 0 || n_strong < 0 || n_weak < 0) return fail(std::string(me) + "negative size", -2);
+  if (P < 1 || P > 4) return fail(std::string(me) + "n_possible must be in [1, 4]", -2);
+  if (solver != 0) return fail(std::string(me) + "only solver 0 (trf) solves this problem", -2);
+  if (C < 1 || C > 16) return fail(std::string(me) + "1 <= cameras <= 16", -2);
+  if (J > 32 || n_strong + n_weak > 64) return fail(std::string(me) + "at most 32 joints and 64 constraints", -2);
+  if (n_deriv_smooth < 1 || n_deriv_smooth > 3) return fail(std::string(me) + "n_deriv_smooth must be 1..3", -2);
+  if (reproj_loss < 0 || reproj_loss > 2) return fail(std::string(me) + "loss must be 0 linear, 1 soft_l1, 2 huber", -2);
+  if (!(reproj_error_threshold > 0)) return fail(std::string(me) + "reproj_error_threshold must be > 0", -2);
+  if (max_nfev < 0) return fail(std::string(me) + "max_nfev must be >= 0", -2);
+  if (n_strong + n_weak > 0 && !constraints) return fail(std::string(me) + "null constraints");
+  for (int k = 0; k < 2 * (n_strong + n_weak); ++k)
+    if (constraints[k] < 0 || constraints[k] >= J) return fail(std::string(me) + "constraint joint out of range", -2);
+  if ((int64_t)B * F * J == 0) return 0;
+  if (F <= n_deriv_smooth) return fail(std::string(me) + "needs more frames than n_deriv_smooth", -2);
+  if ((int64_t)C * F * J * P > (int64_t)1 << 27) return fail(std::string(me) + "too many candidates per animal", -2);
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (ctx->optim_ws.ensure(mq::optim_possible_workspace_bytes(B, F, J, C, P, n_strong + n_weak)))
+    return fail("optim workspace alloc failed", -5);
+  const int rc = mq::optim_points_possible(cams, C, p2d, x, alphas_norm, B, F, J, P, constraints, n_strong, n_weak,
+                                           scale_smooth_full, scale_length, scale_length_weak, reproj_error_threshold,
+                                           reproj_loss, n_deriv_smooth, max_nfev, ftol, ctx->optim_ws.p, stats,
+                                           (hipStream_t)stream);
+  if (rc != 0) return fail(std::string(me) + "solver failed (" + std::to_string(rc) + ")", -6);
+  return 0;
+}
+
 int mq_attention_bf16(mq_ctx* ctx, const uint16_t* qkv, uint16_t* out, int n_img, int tokens, int dim, int heads,
                       void* stream) {
   if (!ctx || !qkv || !out) return fail("mq_attention_bf16: null argument");

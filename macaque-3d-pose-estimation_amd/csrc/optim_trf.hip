@@ -34,6 +34,7 @@
 #include "camera.hpp"
 #include "common.hpp"
 #include "optim_dev.hpp"
+#include "trf_host.hpp"
 
 namespace mq {
 namespace {
@@ -1466,13 +1467,7 @@ int optim_points_trf(const double* cams, int C, const double* p2d, double* x, in
   D.atol = 1e-6;
   D.btol = 1e-6;
   D.ctol = 1.0 / 1e8;
-  {
-    int binom = 1;
-    for (int m = 0; m <= n_deriv; ++m) {
-      D.c[m] = (((n_deriv - m) & 1) ? -1.0 : 1.0) * binom;
-      binom = binom * (n_deriv - m) / (m + 1);
-    }
-  }
+  trf_diff_coefficients(n_deriv, D.c);
   const int NB = D.NB;
   const size_t NVB = (size_t)B * D.NV, MB = (size_t)B * F * D.MR;
   double* w = static_cast<double*>(ws);
@@ -1746,21 +1741,7 @@ int optim_points_trf(const double* cams, int C, const double* p2d, double* x, in
       ctl[4 * b] = ctl[4 * b + 1] = ctl[4 * b + 2] = ctl[4 * b + 3] = 0.0;
       doneh[b] = act[b] ? 0 : 1;
       if (!act[b]) continue;
-      const double a = areg[b];
-      const double bq = -gnorm2[b];
-      const double to_tr = Delta[b] / std::sqrt(gnorm2[b]);
-      double ag = 0.0 * (a * 0.0 + bq);
-      const double y1 = to_tr * (a * to_tr + bq);
-      if (y1 < ag) ag = y1;
-      if (a != 0) {
-        const double ext = -0.5 * bq / a;
-        if (0 < ext && ext < to_tr) {
-          const double y2 = ext * (a * ext + bq);
-          if (y2 < ag) ag = y2;
-        }
-      }
-      const double reg = -ag / (Delta[b] * Delta[b]);
-      damp[b] = std::sqrt(0.0 + reg);
+      damp[b] = trf_regularize_damp(areg[b], gnorm2[b], Delta[b]);
       ctl[4 * b] = damp[b];
       ctl[4 * b + 1] = std::sqrt(2.0 * cost[b]);  // norm(f)
       ctl[4 * b + 2] = std::min(rows[b], (double)nparam);
@@ -1856,15 +1837,8 @@ int optim_points_trf(const double* cams, int C, const double* p2d, double* x, in
         cost_new[b] = cn;
         actual[b] = cost[b] - cn;
         double ratio;
-        if (pred[b] > 0) ratio = actual[b] / pred[b];
-        else if (pred[b] == actual[b] && actual[b] == 0) ratio = 1;
-        else ratio = 0;
-        double Dn = Delta[b];
-        if (ratio < 0.25) Dn = 0.25 * sh;
-        else if (ratio > 0.75 && sh > 0.95 * Delta[b]) Dn *= 2.0;
-        const bool ft = actual[b] < ftol * cost[b] && ratio > 0.25;
-        const bool xt_ok = sh < xtol * (xtol + xnorm[b]);
-        const int term = (ft && xt_ok) ? 4 : ft ? 2 : xt_ok ? 3 : 0;
+        const double Dn = trf_update_tr_radius(Delta[b], actual[b], pred[b], sh, sh > 0.95 * Delta[b], ratio);
+        const int term = trf_check_termination(actual[b], cost[b], sh, xnorm[b], ratio, ftol, xtol);
         if (term) {
           status[b] = term;
           trial[b] = 0;

@@ -31,7 +31,7 @@ EXPORTED = [
     "mq_overlay_primitives_labelled", "mq_overlay_render_labelled", "mq_resize_bilinear",
     "mq_bundle_adjust",
     "mq_jpeg_encode", "mq_jpeg_parse", "mq_jpeg_decode",
-    "mq_decode_udp_topk", "mq_viterbi_filter_multi", "mq_triangulate_possible",
+    "mq_decode_udp_topk", "mq_viterbi_filter_multi", "mq_triangulate_possible", "mq_optim_points_possible",
 ]
 
 
@@ -136,6 +136,8 @@ _SIGS = {
     "mq_triangulate_possible": (i32, [vp, vp, i32, vp, i32, i32, i32, f64, vp, vp, vp, vp, vp]),
     "mq_optim_points": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, vp, i32, i32, vp, f64, f64, f64, i32, i32, i32,
                               i32, f64, i32, vp, vp]),
+    "mq_optim_points_possible": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, vp, i32, i32, vp, f64, f64, f64,
+                                       i32, i32, i32, f64, i32, vp, vp]),
 }
 
 

@@ -518,6 +518,23 @@ class CameraGroup:
                                 reproj_loss=reproj_loss, n_deriv_smooth=n_deriv_smooth, scores=scores,
                                 verbose=verbose)
 
+    def optim_points_possible(self, points, p3ds, constraints=(), constraints_weak=(), scale_smooth=4,
+                              scale_length=2, scale_length_weak=0.5, reproj_error_threshold=15,
+                              reproj_loss='soft_l1', n_deriv_smooth=1, scores=None, verbose=False):
+        """cameras.py:1417-1513 on the GPU: points CxFxJxPx2 (NaN = absent candidate, P <= 4), p3ds FxJx3 ->
+        (p3ds_new FxJx3, alphas_norm CxFxJxP) (see mqhip.optim)."""
+        from .optim import optim_points_possible_gpu
+        return optim_points_possible_gpu(self, points, p3ds, constraints=constraints,
+                                         constraints_weak=constraints_weak, scale_smooth=scale_smooth,
+                                         scale_length=scale_length, scale_length_weak=scale_length_weak,
+                                         reproj_error_threshold=reproj_error_threshold, reproj_loss=reproj_loss,
+                                         n_deriv_smooth=n_deriv_smooth, scores=scores, verbose=verbose)
+
+    def triangulate_optim(self, points, init_ransac=False, init_progress=False, **kwargs):
+        """cameras.py:1516-1556: triangulate (or triangulate_ransac), then optim_points(**kwargs)."""
+        from .optim import triangulate_optim
+        return triangulate_optim(self, points, init_ransac=init_ransac, init_progress=init_progress, **kwargs)
+
     def optim_points_jointlenfix(self, points, p3ds, joint_len, constraints=(), constraints_weak=(), scale_smooth=4,
                                  scale_length=2, scale_length_weak=0.5, reproj_error_threshold=15,
                                  reproj_loss='soft_l1', n_deriv_smooth=1, scores=None, verbose=False):

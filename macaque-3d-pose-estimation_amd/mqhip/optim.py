@@ -17,6 +17,11 @@ Two solvers (ABI 7):
 
 ``optim_points_batch`` refines several animals in one call (they are
 independent problems sharing the cameras).
+
+``optim_points_possible_batch`` is CameraGroup.optim_points_possible (cameras.py:1417-1513): the same refinement
+over up to 4 candidate 2D peaks per (camera, frame, joint), a softmax weight per candidate among the variables
+(``mq_optim_points_possible``, csrc/optim_possible.hip; trf only).  ``triangulate_optim`` (cameras.py:1516-1556)
+chains triangulate / triangulate_ransac and optim_points.
 """
 from __future__ import annotations
 
@@ -143,3 +148,110 @@ def optim_points_gpu(cgroup, points, p3ds, constraints=(), constraints_weak=(), 
                                 reproj_error_threshold, reproj_loss, n_deriv_smooth, joint_len=joint_len,
                                 max_iter=max_iter, ftol=ftol, verbose=verbose, max_nfev=max_nfev)
     return p3[0], jl[0]
+
+
+def optim_points_possible_batch(cgroup, points, p3ds, constraints=(), constraints_weak=(), scale_smooth=4,
+                                scale_length=2, scale_length_weak=0.5, reproj_error_threshold=15,
+                                reproj_loss="soft_l1", n_deriv_smooth=1, scores=None, verbose=False,
+                                return_stats=False, solver=None, max_nfev=None, ftol=1e-3):
+    """points (B,C,F,J,P,2) candidate 2D peaks with NaN for an absent candidate (any pattern), p3ds (B,F,J,3)
+    initial triangulation.  Returns p3ds_new (B,F,J,3), alphas_norm (B,C,F,J,P) -- the softmax weight of every
+    candidate, NaN at NaN candidates -- and joint_len (B, n_strong+n_weak), which the reference drops; with
+    return_stats also the (B, 8) stats of optim_points_batch and scale_smooth_full.  x0 and scale_smooth_full
+    are optim_points' (prepare_batch); the alphas start at 0 (cameras.py:1699-1712).  Only the trf solver
+    solves this problem; P <= 4."""
+    points = np.asarray(points, dtype=np.float64)
+    p3ds = np.asarray(p3ds, dtype=np.float64)
+    if points.ndim != 6 or points.shape[-1] != 2:
+        raise ValueError(f"points must be (B, C, F, J, P, 2), got {points.shape}")
+    B, C, F, J, P, _ = points.shape
+    assert C == len(cgroup.cameras), (
+        "Invalid points shape, first dim should be equal to number of cameras ({}), but shape is {}".format(
+            len(cgroup.cameras), points.shape[1:]))
+    assert p3ds.shape == (B, F, J, 3)
+    if scores is not None:
+        raise NotImplementedError("score-weighted reprojection is disabled on the reference path (step4:252)")
+    if reproj_loss not in LOSSES:
+        raise ValueError(f"unknown reproj_loss {reproj_loss!r}")
+    solver = "trf" if solver is None else solver
+    if solver != "trf":
+        raise ValueError(f"optim_points_possible has the trf solver only, not {solver!r}")
+    if not 1 <= P <= 4:
+        raise ValueError(f"n_possible must be in [1, 4], got {P}")
+    if F <= int(n_deriv_smooth):
+        raise ValueError(f"needs more frames ({F}) than n_deriv_smooth ({n_deriv_smooth})")
+    cons, consw = _pairs(constraints), _pairs(constraints_weak)
+    nS, nW = len(cons), len(consw)
+    xs, ssf = prepare_batch(p3ds, cons, consw, scale_smooth)
+    dev = cgroup._dev()
+    ctx = cgroup._ctx()
+    x_d = torch.from_numpy(xs).to(dev)
+    p2_d = torch.from_numpy(np.ascontiguousarray(points)).to(dev)
+    an_d = torch.empty((B, C, F, J, P), dtype=torch.float64, device=dev)
+    cams = cgroup.cams_tensor()
+    allc = np.ascontiguousarray(np.vstack([cons, consw]).astype(np.int32)) if nS + nW else np.zeros((1, 2), np.int32)
+    ssf_h = np.ascontiguousarray(np.array(ssf, dtype=np.float64))
+    stats = np.zeros((B, 8), dtype=np.float64)
+    import ctypes
+    import time
+    t0 = time.perf_counter()
+    rc = ctx.lib.mq_optim_points_possible(
+        ctx.handle, _lib.ptr(cams), C, _lib.ptr(p2_d), _lib.ptr(x_d), _lib.ptr(an_d), B, F, J, P,
+        allc.ctypes.data_as(ctypes.c_void_p), nS, nW, ssf_h.ctypes.data_as(ctypes.c_void_p),
+        float(scale_length), float(scale_length_weak), float(reproj_error_threshold), LOSSES[reproj_loss],
+        int(n_deriv_smooth), int(max_nfev) if max_nfev else 0, float(ftol), SOLVERS[solver],
+        stats.ctypes.data_as(ctypes.c_void_p), _lib.stream_ptr(dev))
+    _lib.check(rc, "mq_optim_points_possible")
+    x = x_d.cpu().numpy()
+    an = an_d.cpu().numpy()
+    if CALL_LOG is not None:
+        CALL_LOG.append({"B": B, "F": F, "J": J, "P": P, "solver": "trf-possible",
+                         "iterations": stats[:, 2].astype(int).tolist(), "status": stats[:, 3].astype(int).tolist(),
+                         "nfev": stats[:, 4].astype(int).tolist(), "lsmr": stats[:, 6].astype(int).tolist(),
+                         "ms": round((time.perf_counter() - t0) * 1e3, 2)})
+    if verbose:
+        for b in range(B):
+            print(f"optim_points_possible[{b}]: cost {stats[b, 0]:.6g} -> {stats[b, 1]:.6g} in {int(stats[b, 2])} "
+                  f"iterations, status {int(stats[b, 3])}")
+    out = x[:, :F * J * 3].reshape(B, F, J, 3), an, x[:, F * J * 3:]
+    if return_stats:
+        return out + (stats, ssf)
+    return out
+
+
+def optim_points_possible_gpu(cgroup, points, p3ds, constraints=(), constraints_weak=(), scale_smooth=4,
+                              scale_length=2, scale_length_weak=0.5, reproj_error_threshold=15,
+                              reproj_loss="soft_l1", n_deriv_smooth=1, scores=None, verbose=False):
+    """CameraGroup.optim_points_possible signature (cameras.py:1417): points (C,F,J,P,2), p3ds (F,J,3)
+    -> (p3ds_new (F,J,3), alphas_norm (C,F,J,P))."""
+    points = np.asarray(points)
+    assert points.shape[0] == len(cgroup.cameras), (
+        "Invalid points shape, first dim should be equal to number of cameras ({}), but shape is {}".format(
+            len(cgroup.cameras), points.shape))
+    p3, an, _ = optim_points_possible_batch(cgroup, points[None], np.asarray(p3ds)[None], constraints,
+                                            constraints_weak, scale_smooth, scale_length, scale_length_weak,
+                                            reproj_error_threshold, reproj_loss, n_deriv_smooth, scores=scores,
+                                            verbose=verbose)
+    return p3[0], an[0]
+
+
+def triangulate_optim(cgroup, points, init_ransac=False, init_progress=False, **kwargs):
+    """CameraGroup.triangulate_optim (cameras.py:1516-1556): points (C,F,J,2) -> triangulate (or, with
+    init_ransac, triangulate_ransac, whose picked 2D points then replace the input) -> optim_points(**kwargs).
+    With fewer than 20 finite initial points it warns and returns the initial (F,J,3) points."""
+    points = np.asarray(points)
+    assert points.shape[0] == len(cgroup.cameras), (
+        "Invalid points shape, first dim should be equal to number of cameras ({}), but shape is {}".format(
+            len(cgroup.cameras), points.shape))
+    n_cams, n_frames, n_joints, _ = points.shape
+    points_shaped = points.reshape(n_cams, n_frames * n_joints, 2)
+    if init_ransac:
+        p3ds, picked, p2ds, errors = cgroup.triangulate_ransac(points_shaped, progress=init_progress)
+        points = p2ds.reshape(points.shape)
+    else:
+        p3ds = cgroup.triangulate(points_shaped, progress=init_progress)
+    p3ds = p3ds.reshape((n_frames, n_joints, 3))
+    if np.sum(np.isfinite(p3ds[:, :, 0])) < 20:
+        print("warning: not enough 3D points to run optimization")
+        return p3ds
+    return cgroup.optim_points(points, p3ds, **kwargs)

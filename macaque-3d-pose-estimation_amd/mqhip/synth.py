@@ -275,6 +275,42 @@ def make_kp2d(cams, skel, noise_px: float = 2.0, drop: float = 0.1, seed: int = 
     return out
 
 
+def make_candidates(cams, skel, n_possible=2, noise_px=1.0, p_swap=0.2, p_decoy=0.3, p_missing=0.1, seed=0):
+    """Candidate 2D peaks for optim_points_possible: skel (F, J, 3) -> points (C, F, J, P, 2) with NaN for an
+    absent candidate, and true_slot (C, F, J), the slot holding the true point (-1: the cell is missing).
+    Slot 0 is a decoy 40-100 px away in p_swap of the cells, with the true point in slot 1 there; of the other
+    cells p_decoy carry a decoy in slot 1; every further slot holds a decoy in half of the cells whose previous
+    slot is filled (so slot 0 is finite wherever any slot is); p_missing of the cells are NaN in every slot."""
+    rng = np.random.default_rng(seed)
+    F, J, _ = skel.shape
+    C, P = len(cams), n_possible
+    pts = np.full((C, F, J, P, 2), np.nan)
+    true_slot = np.zeros((C, F, J), dtype=np.int64)
+
+    def decoy():
+        r, th = rng.uniform(40, 100, (F, J)), rng.uniform(0, 2 * np.pi, (F, J))
+        return np.stack([r * np.cos(th), r * np.sin(th)], axis=-1)
+
+    for c, cam in enumerate(cams):
+        uv = project_numpy(cam, skel.reshape(-1, 3)).reshape(F, J, 2) + rng.normal(0, noise_px, (F, J, 2))
+        swap = (rng.uniform(0, 1, (F, J)) < p_swap) & (P >= 2)
+        pts[c, :, :, 0] = np.where(swap[..., None], uv + decoy(), uv)
+        true_slot[c] = swap
+        filled = np.ones((F, J), dtype=bool)
+        for p in range(1, P):
+            d = uv + decoy()
+            has = filled & (rng.uniform(0, 1, (F, J)) < (p_decoy if p == 1 else 0.5))
+            if p == 1:
+                has = has | swap
+                d = np.where(swap[..., None], uv, d)
+            pts[c, :, :, p] = np.where(has[..., None], d, np.nan)
+            filled = has
+        missing = rng.uniform(0, 1, (F, J)) < p_missing
+        pts[c][missing] = np.nan
+        true_slot[c][missing] = -1
+    return pts, true_slot
+
+
 def expand_boxes(boxes_xyxy_int, min_margin=0.20, max_margin=0.50, desired_ar=192.0 / 256.0):
     """Box expansion + aspect fix of step1_proc2d.py:270-292 (consts :71-73).
 
