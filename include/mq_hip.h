@@ -715,6 +715,29 @@ int mq_bundle_adjust(mq_ctx* ctx, int mode, int n_cams, int n_points, double* ca
                      const double* obs, const uint8_t* use, int fix_cam0, double ftol, double xtol, int max_iter,
                      double* resid, double* info, void* stream);
 
+/* Bundle adjustment of a camera group on 2D points (aniposelib cameras.py:894-980, CameraGroup.bundle_adjust with
+ * its _error_fun_bundle, extra = None, loss = 'linear'): the solver of mq_bundle_adjust on the reference's
+ * parametrisation.  Every camera and every point is an unknown (no camera is fixed: the damping carries the
+ * 7-dimensional gauge); residual = projection - pixel on the reduced model Camera.set_params leaves
+ * (:290-299, :392-403, :518-529).
+ *   cam_fixed  : HOST float64 (n_cams, 11): the model (0 omnidir, 1 pinhole, 2 fisheye, the camera rows' ids),
+ *                then what the solve does not move: cx, cy (pinhole, fisheye; the rest unused) or K00, K01, K02,
+ *                K11, K12, xi, D[4] (omnidir)
+ *   cam_params : HOST float64 (n_cams, 9), in / out: rvec, tvec, f, k1, k2.  pinhole: u = f x (1 + k1 r2 + k2 r2^2)
+ *                + cx on x = Xc0 / Xc2; fisheye: u = f x theta_d / r + cx, theta_d = theta (1 + k1 theta^2 + k2
+ *                theta^4), theta = atan r (theta_d / r = 1 at r <= 1e-8); omnidir: cv2.omnidir.projectPoints with
+ *                the fixed K, xi, D -- f, k1, k2 do not enter (:509-516)
+ *   free_mask  : HOST uint8 (n_cams * 9): the columns the solve may move.  Slot 8 is free only with extra_dist;
+ *                slots 6-8 of an omnidir camera must be frozen (-2 otherwise); columns of a camera nobody observes
+ *                are removed as well
+ *   points3d, obs, use, ftol, xtol, max_iter, resid, info: as mq_bundle_adjust.  A point one camera sees is legal:
+ *                its 3 x 3 block is rank 2 and moves through the damping alone; a block that cannot be inverted
+ *                counts as a rejected step
+ * Argument errors return -2.  The same bits on every call.  Synchronises stream. */
+int mq_bundle_adjust_group(mq_ctx* ctx, int n_cams, int n_points, const double* cam_fixed, double* cam_params,
+                           const uint8_t* free_mask, double* points3d, const double* obs, const uint8_t* use,
+                           double ftol, double xtol, int max_iter, double* resid, double* info, void* stream);
+
 /* ---- Motion-JPEG frames (csrc/jpeg.hip): a baseline JPEG encoder for the overlay frames, so that only the
  * compressed stream leaves the device.  tests/jpeg_ref.py is the numpy restatement, equal byte for byte: integer
  * arithmetic only, no atomics on global memory, the same bits on every call.

@@ -1877,6 +1877,38 @@ int mq_bundle_adjust(mq_ctx* ctx, int mode, int n_cams, int n_points, double* ca
   return 0;
 }
 
+int mq_bundle_adjust_group(mq_ctx* ctx, int n_cams, int n_points, const double* cam_fixed, double* cam_params,
+                           const uint8_t* free_mask, double* points3d, const double* obs, const uint8_t* use,
+                           double ftol, double xtol, int max_iter, double* resid, double* info, void* stream) {
+  if (!ctx) return fail("mq_bundle_adjust_group: null ctx");
+  if (n_cams < 1 || n_cams > mq::BA_MAXC_API) return fail("mq_bundle_adjust_group: n_cams must be in [1, 16]", -2);
+  if (n_points < 1 || n_points > (1 << 24)) return fail("mq_bundle_adjust_group: n_points must be in [1, 2^24]", -2);
+  if (!cam_fixed || !cam_params || !free_mask || !points3d || !obs || !use || !info)
+    return fail("mq_bundle_adjust_group: null argument");
+  if (!(ftol >= 0.0) || !(xtol >= 0.0) || max_iter < 0)
+    return fail("mq_bundle_adjust_group: bad tolerance or max_iter", -2);
+  constexpr int P = mq::BA_GP_API, F = mq::BA_GFIX_API;
+  for (int c = 0; c < n_cams; ++c) {
+    const double model = cam_fixed[c * F];
+    if (model != 0.0 && model != 1.0 && model != 2.0)
+      return fail("mq_bundle_adjust_group: model must be 0 (omnidir), 1 (pinhole) or 2 (fisheye)", -2);
+    for (int q = 1; q < F; ++q)
+      if (!std::isfinite(cam_fixed[c * F + q])) return fail("mq_bundle_adjust_group: non-finite fixed camera data", -2);
+    for (int p = 0; p < P; ++p)
+      if (!std::isfinite(cam_params[c * P + p])) return fail("mq_bundle_adjust_group: non-finite camera parameter", -2);
+    // an omnidir camera projects with K, xi, D: f, k1, k2 do not enter its residual (cameras.py:509-529)
+    if (model == 0.0 && (free_mask[c * P + 6] || free_mask[c * P + 7] || free_mask[c * P + 8]))
+      return fail("mq_bundle_adjust_group: slots 6-8 of an omnidir camera must be frozen", -2);
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (ctx->ba_ws.ensure(mq::bundle_workspace_bytes(2, n_cams, n_points)))
+    return fail("mq_bundle_adjust_group: out of device memory", -5);
+  const int rc = mq::bundle_adjust_group(n_cams, n_points, cam_params, cam_fixed, free_mask, points3d, obs, use, ftol,
+                                         xtol, max_iter, resid, info, ctx->ba_ws.p, (hipStream_t)stream);
+  if (rc != 0) return fail("mq_bundle_adjust_group: solver failed (" + std::to_string(rc) + ")", rc == -5 ? -5 : -6);
+  return 0;
+}
+
 }  // extern "C"
 
 // error reporting for the host-only translation units (optim_host.cpp)

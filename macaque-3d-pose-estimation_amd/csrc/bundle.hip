@@ -1,6 +1,8 @@
 // Bundle adjustment of the camera rig on marker traces: multicam_toolbox.optimize_extrinsic (:488-636, mode 0:
 // 6 extrinsic parameters per camera, residual on undistorted points) and optimize_all_camera_params (:638-824,
-// mode 1: 16 parameters per camera, residual = omnidir projection - pixel).  float64 throughout.
+// mode 1: 16 parameters per camera, residual = omnidir projection - pixel), and aniposelib's
+// CameraGroup.bundle_adjust (cameras.py:894-980, mode 2: rvec, tvec, f, k1, k2 per camera, a camera model per
+// camera, residual = projection of the reduced model - pixel).  float64 throughout.
 //
 // Solver: Levenberg-Marquardt on the Schur complement of the point blocks, Marquardt (diagonal) scaling.  It
 // stands in for scipy's least_squares(method='trf', x_scale='jac'); it is not a restatement of it.  With
@@ -15,8 +17,9 @@
 //                  index order into this workgroup's partial.  A workgroup takes chunks g, g + G, ... in order.
 //   ba_reduce      sums the G partials in index order: no floating-point atomics anywhere, so the reduced system
 //                  -- and with it every output -- is the same bits on every run.
-//   host           Cholesky of the <= 256 free camera unknowns (frozen and unobserved columns removed), the
-//                  gain ratio, accept / reject and the lambda update (Nielsen's rule, floor 1/10).
+//   host           Cholesky of the <= 256 free camera unknowns (columns outside the free mask and unobserved
+//                  columns removed), the gain ratio, accept / reject and the lambda update (Nielsen's rule,
+//                  floor 1/10).
 //   ba_backsub     delta X_i = -V_i*^-1 g_i - Y_ci^T delta c_c per point, the trial points, and per-workgroup
 //                  tree sums of the points' share of the predicted decrease and of |delta X|^2, |X|^2.
 //   ba_cost        cost 1/2 sum r^2 at the trial cameras and points, per-workgroup tree sums (fixed pairing).
@@ -30,17 +33,32 @@
 
 #include "bundle.hpp"
 #include "bundle_dev.hpp"
+#include "camera.hpp"
 
 namespace mq {
 namespace {
 
 static_assert(BA_MAXC == BA_MAXC_API, "the entry point's camera limit is the kernels' shared-array size");
+static_assert(BA_GP == BA_GP_API && BA_GFIX == BA_GFIX_API, "the entry point's mode-2 row is the kernels'");
+static_assert(BA_CAM_OMNIDIR == CAM_OMNIDIR && BA_CAM_PINHOLE == CAM_PINHOLE && BA_CAM_FISHEYE == CAM_FISHEYE,
+              "mode 2 uses camera.hpp's model ids");
 constexpr int BA_T = 256;      // threads per workgroup
 constexpr int BA_CHUNK = 64;   // points per chunk (phase A threads)
 constexpr int BA_MAXG = 128;   // workgroups (partials) of ba_linearise
 constexpr int BA_PT = 10;      // per-point record: V*^-1 g (3), diag V (3), g (3), cost
 
-__host__ __device__ inline int ba_params(int mode) { return mode ? 16 : 6; }
+// shared-memory stride of a camera: its parameters, and in mode 2 the fixed data next to them
+__host__ __device__ constexpr int ba_stride(int mode) { return mode == 2 ? BA_GROW : BA_MAXP; }
+
+// one camera's row into shared memory: P parameters from cam, in mode 2 followed by its BA_GFIX fixed doubles
+template <int MODE>
+__device__ __forceinline__ void load_camera(double* row, const double* __restrict__ cam,
+                                            const double* __restrict__ fix, int c) {
+  constexpr int P = ba_nparams(MODE);
+  for (int p = 0; p < P; ++p) row[p] = cam[c * P + p];
+  if (MODE == 2)
+    for (int q = 0; q < BA_GFIX; ++q) row[P + q] = fix[c * BA_GFIX + q];
+}
 
 // fixed-pairing tree sum of sm[0 .. BA_T) into sm[0]
 __device__ __forceinline__ void tree_sum(double* sm, int tid) {
@@ -52,21 +70,23 @@ __device__ __forceinline__ void tree_sum(double* sm, int tid) {
 }
 
 template <int MODE>
-__global__ __launch_bounds__(BA_T) void ba_linearise(const double* __restrict__ cam, const double* __restrict__ X,
+__global__ __launch_bounds__(BA_T) void ba_linearise(const double* __restrict__ cam, const double* __restrict__ fix,
+                                                     const double* __restrict__ X,
                                                      const double* __restrict__ obs,
                                                      const uint8_t* __restrict__ use, int C, int N, double lambda,
                                                      int n_chunks, double* obsbuf, double* ptbuf,
                                                      double* __restrict__ partial) {
-  constexpr int P = MODE ? 16 : 6;
+  constexpr int P = ba_nparams(MODE);
+  constexpr int CS = ba_stride(MODE);
   constexpr int OS = 9 * P;  // per observation: W (3P) | Y (3P) | A row 0 (P) | A row 1 (P) | A^T r (P)
-  __shared__ double sC[BA_MAXC * BA_MAXP];
+  __shared__ double sC[BA_MAXC * CS];
   __shared__ double sR[BA_MAXC * 9];
   __shared__ double sdR[BA_MAXC * 27];
   const int tid = threadIdx.x;
   const int n = C * P;
   const int L = n * n + 3 * n + 1;
   if (tid < C) {
-    for (int p = 0; p < P; ++p) sC[tid * BA_MAXP + p] = cam[tid * P + p];
+    load_camera<MODE>(sC + tid * CS, cam, fix, tid);
     ba_rotation_jac(cam + tid * P, sR + tid * 9, sdR + tid * 27);
   }
   __syncthreads();
@@ -80,11 +100,13 @@ __global__ __launch_bounds__(BA_T) void ba_linearise(const double* __restrict__ 
       const int i = base + tid;
       const double Xi[3] = {X[3 * (size_t)i], X[3 * (size_t)i + 1], X[3 * (size_t)i + 2]};
       double V[6] = {0, 0, 0, 0, 0, 0}, g[3] = {0, 0, 0}, cost = 0.0;
+      bool seen = false;
       for (int c = 0; c < C; ++c) {
         double* o = obsbuf + ((size_t)i * C + c) * OS;
         if (use[(size_t)i * C + c]) {
+          seen = true;
           double r[2], A[2 * P], B[6];
-          ba_obs_jac<MODE>(sC + c * BA_MAXP, sR + c * 9, sdR + c * 27, Xi, obs + ((size_t)c * N + i) * 2, r, A, B);
+          ba_obs_jac<MODE>(sC + c * CS, sR + c * 9, sdR + c * 27, Xi, obs + ((size_t)c * N + i) * 2, r, A, B);
           V[0] += B[0] * B[0] + B[3] * B[3];
           V[1] += B[0] * B[1] + B[3] * B[4];
           V[2] += B[0] * B[2] + B[3] * B[5];
@@ -114,6 +136,9 @@ __global__ __launch_bounds__(BA_T) void ba_linearise(const double* __restrict__ 
       iv[5] = a * d - b * b;
       const double det = a * iv[0] + b * iv[1] + c2 * iv[2];
       const double idet = det > 0.0 ? 1.0 / det : 0.0;  // a point nobody sees: no step, no contribution
+      // Mode 2 keeps points one camera sees: V is rank 2 and only the damping makes V* invertible.  Where the
+      // inverse fails for a point that is seen, the cost slot carries NaN and the host rejects the step.
+      if (MODE == 2 && seen && !(det > 0.0 && isfinite(idet))) cost = __builtin_nan("");
       for (int k = 0; k < 6; ++k) iv[k] *= idet;
       double* pt = ptbuf + (size_t)i * BA_PT;
       pt[0] = iv[0] * g[0] + iv[1] * g[1] + iv[2] * g[2];
@@ -233,17 +258,18 @@ __global__ __launch_bounds__(BA_T) void ba_backsub(const double* __restrict__ ob
 }
 
 template <int MODE>
-__global__ __launch_bounds__(BA_T) void ba_cost(const double* __restrict__ cam, const double* __restrict__ X,
-                                                const double* __restrict__ obs, const uint8_t* __restrict__ use,
-                                                int C, int N, double* __restrict__ resid,
-                                                double* __restrict__ pc) {
-  constexpr int P = MODE ? 16 : 6;
-  __shared__ double sC[BA_MAXC * BA_MAXP];
+__global__ __launch_bounds__(BA_T) void ba_cost(const double* __restrict__ cam, const double* __restrict__ fix,
+                                                const double* __restrict__ X, const double* __restrict__ obs,
+                                                const uint8_t* __restrict__ use, int C, int N,
+                                                double* __restrict__ resid, double* __restrict__ pc) {
+  constexpr int P = ba_nparams(MODE);
+  constexpr int CS = ba_stride(MODE);
+  __shared__ double sC[BA_MAXC * CS];
   __shared__ double sR[BA_MAXC * 9];
   __shared__ double sm[BA_T];
   const int tid = threadIdx.x;
   if (tid < C) {
-    for (int p = 0; p < P; ++p) sC[tid * BA_MAXP + p] = cam[tid * P + p];
+    load_camera<MODE>(sC + tid * CS, cam, fix, tid);
     ba_rodrigues(cam + tid * P, sR + tid * 9);
   }
   __syncthreads();
@@ -254,7 +280,7 @@ __global__ __launch_bounds__(BA_T) void ba_cost(const double* __restrict__ cam, 
     for (int c = 0; c < C; ++c) {
       double r[2] = {0.0, 0.0};
       if (use[(size_t)i * C + c]) {
-        ba_obs_res<MODE>(sC + c * BA_MAXP, sR + c * 9, Xi, obs + ((size_t)c * N + i) * 2, r);
+        ba_obs_res<MODE>(sC + c * CS, sR + c * 9, Xi, obs + ((size_t)c * N + i) * 2, r);
         cost += 0.5 * (r[0] * r[0] + r[1] * r[1]);
       }
       if (resid) {
@@ -296,11 +322,11 @@ bool chol_solve(std::vector<double>& M, std::vector<double>& b, int nf) {
 }
 
 struct Layout {
-  size_t obsbuf, ptbuf, partial, red, cam_a, cam_b, dc, xt, pr, pc, total;
+  size_t obsbuf, ptbuf, partial, red, cam_a, cam_b, dc, xt, pr, pc, fix, total;
 };
 
 Layout ba_layout(int mode, int C, int N) {
-  const size_t P = ba_params(mode), n = (size_t)C * P, L = n * n + 3 * n + 1;
+  const size_t P = ba_nparams(mode), n = (size_t)C * P, L = n * n + 3 * n + 1;
   const size_t chunks = ((size_t)N + BA_CHUNK - 1) / BA_CHUNK;
   const size_t G = std::max<size_t>(1, std::min<size_t>(chunks, BA_MAXG));
   const size_t G2 = std::max<size_t>(1, ((size_t)N + BA_T - 1) / BA_T);
@@ -321,6 +347,7 @@ Layout ba_layout(int mode, int C, int N) {
   l.xt = take((size_t)N * 3);
   l.pr = take(G2 * 4);
   l.pc = take(G2);
+  l.fix = take(mode == 2 ? (size_t)C * BA_GFIX : 0);
   l.total = at;
   return l;
 }
@@ -331,10 +358,10 @@ Layout ba_layout(int mode, int C, int N) {
   } while (0)
 
 template <int MODE>
-int bundle_adjust_impl(int C, int N, double* cam, double* X, const double* obs, const uint8_t* use, int fix_cam0,
-                       double ftol, double xtol, int max_iter, double* resid, double* info, void* ws_,
-                       hipStream_t s) {
-  constexpr int P = MODE ? 16 : 6;
+int bundle_adjust_impl(int C, int N, double* cam, const double* cam_fixed, const uint8_t* free_mask, double* X,
+                       const double* obs, const uint8_t* use, double ftol, double xtol, int max_iter, double* resid,
+                       double* info, void* ws_, hipStream_t s) {
+  constexpr int P = ba_nparams(MODE);
   const int n = C * P, L = n * n + 3 * n + 1;
   const int n_chunks = (N + BA_CHUNK - 1) / BA_CHUNK;
   const int G = std::max(1, std::min(n_chunks, BA_MAXG));
@@ -344,13 +371,14 @@ int bundle_adjust_impl(int C, int N, double* cam, double* X, const double* obs, 
   double *obsbuf = ws + l.obsbuf, *ptbuf = ws + l.ptbuf, *partial = ws + l.partial, *red = ws + l.red;
   double *cam_cur = ws + l.cam_a, *cam_try = ws + l.cam_b, *dc = ws + l.dc;
   double *x_cur = X, *x_try = ws + l.xt, *pr = ws + l.pr, *pc = ws + l.pc;
+  const double* fix = MODE == 2 ? ws + l.fix : nullptr;
 
   std::vector<double> hcam(cam, cam + n), htry(n), hred(L), hdc(n), hpr((size_t)G2 * 4), hpc(G2);
   std::vector<double> M, rhs;
   std::vector<int> freeidx;
 
   auto cost_at = [&](const double* cam_d, const double* x_d, double* resid_d, double& out) -> int {
-    hipLaunchKernelGGL(ba_cost<MODE>, dim3(G2), dim3(BA_T), 0, s, cam_d, x_d, obs, use, C, N, resid_d, pc);
+    hipLaunchKernelGGL(ba_cost<MODE>, dim3(G2), dim3(BA_T), 0, s, cam_d, fix, x_d, obs, use, C, N, resid_d, pc);
     BA_HIP(hipGetLastError());
     BA_HIP(hipMemcpyAsync(hpc.data(), pc, sizeof(double) * G2, hipMemcpyDeviceToHost, s));
     BA_HIP(hipStreamSynchronize(s));
@@ -360,6 +388,8 @@ int bundle_adjust_impl(int C, int N, double* cam, double* X, const double* obs, 
   };
 
   BA_HIP(hipMemcpyAsync(cam_cur, hcam.data(), sizeof(double) * n, hipMemcpyHostToDevice, s));
+  if (MODE == 2)
+    BA_HIP(hipMemcpyAsync(ws + l.fix, cam_fixed, sizeof(double) * C * BA_GFIX, hipMemcpyHostToDevice, s));
   double cost = 0.0;
   int rc = cost_at(cam_cur, x_cur, nullptr, cost);
   if (rc) return rc;
@@ -368,8 +398,8 @@ int bundle_adjust_impl(int C, int N, double* cam, double* X, const double* obs, 
   int iters = 0, accepted = 0, n_lin = 0, stop = BA_STOP_MAX_ITER, nf = 0;
 
   while (iters < max_iter && N > 0) {
-    hipLaunchKernelGGL(ba_linearise<MODE>, dim3(G), dim3(BA_T), 0, s, cam_cur, x_cur, obs, use, C, N, lambda,
-                       n_chunks, obsbuf, ptbuf, partial);
+    hipLaunchKernelGGL(ba_linearise<MODE>, dim3(G), dim3(BA_T), 0, s, cam_cur, fix, x_cur, obs, use, C, N,
+                       lambda, n_chunks, obsbuf, ptbuf, partial);
     BA_HIP(hipGetLastError());
     hipLaunchKernelGGL(ba_reduce, dim3((L + BA_T - 1) / BA_T), dim3(BA_T), 0, s, partial, G, L, red);
     BA_HIP(hipGetLastError());
@@ -380,12 +410,10 @@ int bundle_adjust_impl(int C, int N, double* cam, double* X, const double* obs, 
     const double* rh = Sm + (size_t)n * n;
     const double* gc = rh + n;
     const double* du = gc + n;
-    // free unknowns: not frozen, and the camera is observed (diag U > 0)
+    // free unknowns: in the free mask, and the camera is observed (diag U > 0)
     freeidx.clear();
-    for (int k = 0; k < n; ++k) {
-      const bool frozen = fix_cam0 && k < 6;
-      if (!frozen && du[k] > 0.0) freeidx.push_back(k);
-    }
+    for (int k = 0; k < n; ++k)
+      if (free_mask[k] && du[k] > 0.0) freeidx.push_back(k);
     nf = (int)freeidx.size();
     if (nf == 0) {
       stop = BA_STOP_LAMBDA;
@@ -398,7 +426,8 @@ int bundle_adjust_impl(int C, int N, double* cam, double* X, const double* obs, 
       for (int b = 0; b <= a; ++b) M[(size_t)a * nf + b] = Sm[(size_t)freeidx[a] * n + freeidx[b]];
     }
     ++iters;
-    bool ok = chol_solve(M, rhs, nf);
+    // mode 2: a seen point whose damped 3 x 3 block could not be inverted (NaN in the cost slot) rejects the step
+    bool ok = (MODE != 2 || std::isfinite(hred[(size_t)L - 1])) && chol_solve(M, rhs, nf);
     double cost_try = 0.0, pred = 0.0, step2 = 0.0, x2 = 0.0;
     if (ok) {
       std::fill(hdc.begin(), hdc.end(), 0.0);
@@ -482,9 +511,21 @@ size_t bundle_workspace_bytes(int mode, int C, int N) { return ba_layout(mode, C
 int bundle_adjust(int mode, int C, int N, double* cam, double* X, const double* obs, const uint8_t* use,
                   int fix_cam0, double ftol, double xtol, int max_iter, double* resid, double* info, void* ws,
                   hipStream_t s) {
+  // fix_cam0 as a column mask: camera 0's rvec and tvec frozen, every other column free
+  std::vector<uint8_t> free_mask((size_t)C * ba_nparams(mode), 1);
+  if (fix_cam0) std::fill(free_mask.begin(), free_mask.begin() + 6, 0);
   if (mode == 0)
-    return bundle_adjust_impl<0>(C, N, cam, X, obs, use, fix_cam0, ftol, xtol, max_iter, resid, info, ws, s);
-  return bundle_adjust_impl<1>(C, N, cam, X, obs, use, fix_cam0, ftol, xtol, max_iter, resid, info, ws, s);
+    return bundle_adjust_impl<0>(C, N, cam, nullptr, free_mask.data(), X, obs, use, ftol, xtol, max_iter, resid,
+                                 info, ws, s);
+  return bundle_adjust_impl<1>(C, N, cam, nullptr, free_mask.data(), X, obs, use, ftol, xtol, max_iter, resid, info,
+                               ws, s);
+}
+
+int bundle_adjust_group(int C, int N, double* cam, const double* cam_fixed, const uint8_t* free_mask, double* X,
+                        const double* obs, const uint8_t* use, double ftol, double xtol, int max_iter,
+                        double* resid, double* info, void* ws, hipStream_t s) {
+  return bundle_adjust_impl<2>(C, N, cam, cam_fixed, free_mask, X, obs, use, ftol, xtol, max_iter, resid, info, ws,
+                               s);
 }
 
 }  // namespace mq

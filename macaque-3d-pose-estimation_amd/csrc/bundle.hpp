@@ -7,6 +7,8 @@
 namespace mq {
 
 constexpr int BA_MAXC_API = 16;  // cameras (OPT_MAXC)
+constexpr int BA_GP_API = 9;     // mode 2: parameter slots per camera
+constexpr int BA_GFIX_API = 11;  // mode 2: fixed doubles per camera (model first)
 
 // stop reasons written to info[3]
 constexpr int BA_STOP_MAX_ITER = 1;  // max_iter trial steps taken
@@ -23,5 +25,13 @@ size_t bundle_workspace_bytes(int mode, int C, int N);
 int bundle_adjust(int mode, int C, int N, double* cam, double* X, const double* obs, const uint8_t* use,
                   int fix_cam0, double ftol, double xtol, int max_iter, double* resid, double* info, void* ws,
                   hipStream_t s);
+
+// Mode 2, aniposelib's CameraGroup.bundle_adjust (cameras.py:894-980): cam is HOST (C, 9) in / out -- rvec, tvec,
+// f, k1, k2; cam_fixed is HOST (C, 11) -- the model (camera.hpp's ids), then cx, cy (pinhole, fisheye) or K00,
+// K01, K02, K11, K12, xi, D[4] (omnidir); free_mask is HOST (C * 9): the columns the solve may move (a column
+// whose camera nobody observes is removed as well).  The rest as bundle_adjust; workspace of mode 2.
+int bundle_adjust_group(int C, int N, double* cam, const double* cam_fixed, const uint8_t* free_mask, double* X,
+                        const double* obs, const uint8_t* use, double ftol, double xtol, int max_iter,
+                        double* resid, double* info, void* ws, hipStream_t s);
 
 }  // namespace mq

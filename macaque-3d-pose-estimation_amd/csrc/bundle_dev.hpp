@@ -8,6 +8,13 @@
 //   xu, yu, k1, k2, p1, p2   -> (xd, yd)             radial + tangential distortion
 //   K                        -> (u, v)               affine: written out
 // and chained by hand.  The stage functions restate camera.hpp's omni_project with its operation order.
+//
+// Mode 2 (aniposelib's CameraGroup.bundle_adjust, cameras.py:894-980) has 9 slots per camera, rvec, tvec, f, k1,
+// k2, and a model per camera (camera.hpp's ids) with the data the solve does not move next to them:
+//   Xc (3)                   -> (x, y)               Xc[:2] / Xc[2], or the omnidir unit-sphere point (xi fixed)
+//   x, y, f, k1, k2 (5)      -> (u, v)               pinhole: f x (1 + k1 r2 + k2 r2^2) + cx;  fisheye: f x
+//                                                    theta_d / r + cx, theta_d = theta (1 + k1 theta^2 + k2
+//                                                    theta^4);  omnidir: fixed K, D on (x, y) alone (2 slots)
 #pragma once
 #include <math.h>
 
@@ -21,6 +28,13 @@ namespace mq {
 
 constexpr int BA_MAXC = 16;  // cameras (OPT_MAXC)
 constexpr int BA_MAXP = 16;  // parameters per camera in mode 1: rvec, tvec, K00, K01, K02, K11, K12, xi, D[4]
+constexpr int BA_GP = 9;     // parameter slots per camera in mode 2: rvec, tvec, f, k1, k2
+constexpr int BA_GFIX = 11;  // mode 2, what the solve does not move: model, then cx, cy (pinhole, fisheye) or
+                             // K00, K01, K02, K11, K12, xi, D[4] (omnidir)
+constexpr int BA_GROW = BA_GP + BA_GFIX;  // a mode-2 camera row: the slots, then the fixed data
+constexpr int BA_CAM_OMNIDIR = 0, BA_CAM_PINHOLE = 1, BA_CAM_FISHEYE = 2;  // camera.hpp's CamModel
+
+constexpr int ba_nparams(int mode) { return mode == 2 ? BA_GP : mode ? 16 : 6; }
 
 template <int N>
 struct Dual {
@@ -88,6 +102,14 @@ BA_HD Dual<N> operator-(double a, const Dual<N>& b) {
   return r;
 }
 template <int N>
+BA_HD Dual<N> operator/(double a, const Dual<N>& b) {
+  Dual<N> r;
+  const double ib = 1.0 / b.v;
+  r.v = a / b.v;
+  for (int i = 0; i < N; ++i) r.d[i] = -(r.v * b.d[i]) * ib;
+  return r;
+}
+template <int N>
 BA_HD Dual<N> operator*(const Dual<N>& a, double b) {
   Dual<N> r;
   r.v = a.v * b;
@@ -122,6 +144,15 @@ BA_HD Dual<N> ba_cos(const Dual<N>& a) {
   for (int i = 0; i < N; ++i) r.d[i] = a.d[i] * s;
   return r;
 }
+template <int N>
+BA_HD Dual<N> ba_atan(const Dual<N>& a) {
+  Dual<N> r;
+  r.v = atan(a.v);
+  const double h = 1.0 / (1.0 + a.v * a.v);
+  for (int i = 0; i < N; ++i) r.d[i] = a.d[i] * h;
+  return r;
+}
+BA_HD double ba_atan(double a) { return atan(a); }
 BA_HD double ba_sqrt(double a) { return sqrt(a); }
 BA_HD double ba_sin(double a) { return sin(a); }
 BA_HD double ba_cos(double a) { return cos(a); }
@@ -182,13 +213,71 @@ BA_HD void ba_omni_distort(const T& xu, const T& yu, const T& k1, const T& k2, c
   yd = yu * (1.0 + k1 * r2 + k2 * r4) + p1 * (r2 + 2.0 * yu * yu) + 2.0 * p2 * xu * yu;
 }
 
-// Residual of one observation.  cp: the camera's P parameters; R: its rotation matrix.
+// Mode 2, pinhole on the reduced model set_params leaves (cameras.py:290-299: fx = fy = f, distortions k1, k2
+// only): pinhole_project's operation order with the terms that are zero left out.
+template <class T>
+BA_HD void ba_group_pinhole(const T& x, const T& y, const T& f, const T& k1, const T& k2, double cx, double cy, T& u,
+                            T& v) {
+  const T r2 = x * x + y * y;
+  const T r4 = r2 * r2;
+  const T cdist = 1.0 + k1 * r2 + k2 * r4;
+  u = (x * cdist) * f + cx;
+  v = (y * cdist) * f + cy;
+}
+
+// Mode 2, fisheye on the reduced model (cameras.py:392-403): fisheye_project's operation order and its rule
+// cdist = 1 at r <= 1e-8, where theta_d / r -> 1 and the derivative with respect to k1, k2 is O(r^2).
+template <class T>
+BA_HD void ba_group_fisheye(const T& x, const T& y, const T& f, const T& k1, const T& k2, double cx, double cy, T& u,
+                            T& v) {
+  const T r2 = x * x + y * y;
+  T cdist = r2 * 0.0 + 1.0;
+  if (sqrt(ba_value(r2)) > 1e-8) {
+    const T r = ba_sqrt(r2);
+    const T th = ba_atan(r);
+    const T th2 = th * th, th3 = th2 * th, th4 = th2 * th2, th5 = th4 * th;
+    const T theta_d = th + k1 * th3 + k2 * th5;
+    cdist = theta_d * (1.0 / r);
+  }
+  u = (x * cdist) * f + cx;
+  v = (y * cdist) * f + cy;
+}
+
+// Mode 2, one camera row's projection of the camera-frame point; g: the row's fixed data (after the model)
+template <class T>
+BA_HD void ba_group_unit(int model, const double* g, const T& x0, const T& x1, const T& x2, T& x, T& y) {
+  if (model == BA_CAM_OMNIDIR) {
+    ba_omni_unit(x0, x1, x2, x0 * 0.0 + g[5], x, y);
+  } else {
+    x = x0 / x2;
+    y = x1 / x2;
+  }
+}
+
+// Residual of one observation.  cp: the camera's P parameters (mode 2: its BA_GROW row); R: its rotation matrix.
 template <int MODE>
 BA_HD void ba_obs_res(const double* cp, const double* R, const double* X, const double* ob, double* r) {
   const double x0 = R[0] * X[0] + R[1] * X[1] + R[2] * X[2] + cp[3];
   const double x1 = R[3] * X[0] + R[4] * X[1] + R[5] * X[2] + cp[4];
   const double x2 = R[6] * X[0] + R[7] * X[1] + R[8] * X[2] + cp[5];
-  if (MODE == 0) {
+  if (MODE == 2) {
+    const int model = (int)cp[BA_GP];
+    const double* g = cp + BA_GP + 1;
+    double x, y, u, v;
+    ba_group_unit(model, g, x0, x1, x2, x, y);
+    if (model == BA_CAM_OMNIDIR) {
+      double xd, yd;
+      ba_omni_distort(x, y, g[6], g[7], g[8], g[9], xd, yd);
+      u = g[0] * xd + g[1] * yd + g[2];
+      v = g[3] * yd + g[4];
+    } else if (model == BA_CAM_PINHOLE) {
+      ba_group_pinhole(x, y, cp[6], cp[7], cp[8], g[0], g[1], u, v);
+    } else {
+      ba_group_fisheye(x, y, cp[6], cp[7], cp[8], g[0], g[1], u, v);
+    }
+    r[0] = u - ob[0];
+    r[1] = v - ob[1];
+  } else if (MODE == 0) {
     r[0] = x0 / x2 - ob[0];
     r[1] = x1 / x2 - ob[1];
   } else {
@@ -205,12 +294,46 @@ BA_HD void ba_obs_res(const double* cp, const double* R, const double* X, const 
 template <int MODE>
 BA_HD void ba_obs_jac(const double* cp, const double* R, const double* dR, const double* X, const double* ob,
                       double* r, double* A, double* B) {
-  constexpr int P = MODE ? 16 : 6;
+  constexpr int P = ba_nparams(MODE);
   const double x0 = R[0] * X[0] + R[1] * X[1] + R[2] * X[2] + cp[3];
   const double x1 = R[3] * X[0] + R[4] * X[1] + R[5] * X[2] + cp[4];
   const double x2 = R[6] * X[0] + R[7] * X[1] + R[8] * X[2] + cp[5];
   double Jq[2][3];  // d (u, v) / d Xc
-  if (MODE == 0) {
+  if (MODE == 2) {
+    const int model = (int)cp[BA_GP];
+    const double* g = cp + BA_GP + 1;
+    Dual<3> x3, y3;
+    ba_group_unit(model, g, dual_var<3>(x0, 0), dual_var<3>(x1, 1), dual_var<3>(x2, 2), x3, y3);
+    double G[2][2];  // d (u, v) / d (x, y)
+    if (model == BA_CAM_OMNIDIR) {  // K, xi, D are not among the slots: columns 6.. are zero and stay frozen
+      Dual<2> xd2, yd2;
+      ba_omni_distort(dual_var<2>(x3.v, 0), dual_var<2>(y3.v, 1), dual_const<2>(g[6]), dual_const<2>(g[7]),
+                      dual_const<2>(g[8]), dual_const<2>(g[9]), xd2, yd2);
+      r[0] = g[0] * xd2.v + g[1] * yd2.v + g[2] - ob[0];
+      r[1] = g[3] * yd2.v + g[4] - ob[1];
+      for (int j = 0; j < 2; ++j) {
+        G[0][j] = g[0] * xd2.d[j] + g[1] * yd2.d[j];
+        G[1][j] = g[3] * yd2.d[j];
+      }
+      for (int j = 6; j < P; ++j) A[0 * P + j] = 0.0, A[1 * P + j] = 0.0;
+    } else {
+      Dual<5> u5, v5;
+      if (model == BA_CAM_PINHOLE)
+        ba_group_pinhole(dual_var<5>(x3.v, 0), dual_var<5>(y3.v, 1), dual_var<5>(cp[6], 2), dual_var<5>(cp[7], 3),
+                         dual_var<5>(cp[8], 4), g[0], g[1], u5, v5);
+      else
+        ba_group_fisheye(dual_var<5>(x3.v, 0), dual_var<5>(y3.v, 1), dual_var<5>(cp[6], 2), dual_var<5>(cp[7], 3),
+                         dual_var<5>(cp[8], 4), g[0], g[1], u5, v5);
+      r[0] = u5.v - ob[0];
+      r[1] = v5.v - ob[1];
+      for (int j = 0; j < 2; ++j) G[0][j] = u5.d[j], G[1][j] = v5.d[j];
+      for (int j = 0; j < 3; ++j) A[0 * P + 6 + j] = u5.d[2 + j], A[1 * P + 6 + j] = v5.d[2 + j];  // f, k1, k2
+    }
+    for (int j = 0; j < 3; ++j) {
+      Jq[0][j] = G[0][0] * x3.d[j] + G[0][1] * y3.d[j];
+      Jq[1][j] = G[1][0] * x3.d[j] + G[1][1] * y3.d[j];
+    }
+  } else if (MODE == 0) {
     const double iz = 1.0 / x2;
     const double x = x0 / x2, y = x1 / x2;
     r[0] = x - ob[0];

@@ -93,3 +93,78 @@ def bundle_adjust(cam_params, points3d, obs, use, mode, fix_cam0=True, ftol=None
         r[keep] = res_d.cpu().numpy()
         info["residuals"] = r
     return cam_h, pts, info
+
+
+# ----------------------------------------------------------------------------- aniposelib's CameraGroup.bundle_adjust
+N_GROUP_PARAMS = 9                 # csrc/bundle_dev.hpp BA_GP: rvec, tvec, f, k1, k2 (cameras.py:279-299)
+N_GROUP_FIXED = 11                 # BA_GFIX: model, then cx, cy or K00, K01, K02, K11, K12, xi, D[4]
+MODEL_OMNIDIR = 0                  # csrc/camera.hpp CamModel
+
+
+def group_free_mask(models, extra_dist):
+    """(C, 9) bool: the slots aniposelib's parametrisation moves.  rvec, tvec, f, k1 of every camera, k2 only
+    with ``extra_dist`` (cameras.py:279-299); an omnidir camera projects with K, xi, D, which set_params does not
+    touch (:509-529), so only its rvec and tvec are free."""
+    models = np.asarray(models).ravel()
+    mask = np.ones((models.size, N_GROUP_PARAMS), dtype=bool)
+    mask[:, 8] = bool(extra_dist)
+    mask[models == MODEL_OMNIDIR, 6:] = False
+    return mask
+
+
+def bundle_adjust_group(cam_fixed, cam_params, free_mask, points3d, obs, use, ftol=1e-4, max_iter=1000, xtol=1e-8,
+                        return_residuals=False, device: int = 0):
+    """The solve inside aniposelib's ``CameraGroup.bundle_adjust`` (cameras.py:894-980, ``extra=None``,
+    ``loss='linear'``) through ``mq_bundle_adjust_group``: refine ``cam_params`` (C, 9) -- rvec, tvec, f, k1, k2 --
+    and ``points3d`` (N, 3) on pixel observations ``obs`` (C, N, 2) marked by ``use`` (N, C).
+
+    ``cam_fixed`` (C, 11) holds each camera's model and what the solve does not move (include/mq_hip.h);
+    ``free_mask`` (C, 9) the columns it may move (``group_free_mask``).  Unlike ``bundle_adjust`` every point
+    stays in the solve, as in the reference: a point one camera sees moves through the damping alone, a point
+    nobody sees keeps its value.  No camera is fixed; the 7 gauge freedoms are left to the damping.
+
+    Returns ``(cam_params, points3d, info)`` with ``bundle_adjust``'s info; ``residuals`` are projection - pixel.
+    """
+    import torch
+
+    from . import _lib
+    fixed = np.ascontiguousarray(cam_fixed, dtype=np.float64)
+    cam = np.array(cam_params, dtype=np.float64)
+    mask = np.ascontiguousarray(free_mask, dtype=np.uint8)
+    pts = np.array(points3d, dtype=np.float64)
+    obs = np.ascontiguousarray(obs, dtype=np.float64)
+    use = np.asarray(use, dtype=bool)
+    if cam.ndim != 2 or cam.shape[1] != N_GROUP_PARAMS or not 1 <= cam.shape[0] <= MAX_CAMS:
+        raise ValueError(f"cam_params must be (C <= {MAX_CAMS}, {N_GROUP_PARAMS}), got {cam.shape}")
+    C = cam.shape[0]
+    if fixed.shape != (C, N_GROUP_FIXED) or mask.shape != (C, N_GROUP_PARAMS):
+        raise ValueError(f"cam_fixed must be {(C, N_GROUP_FIXED)} and free_mask {(C, N_GROUP_PARAMS)}, got "
+                         f"{fixed.shape} and {mask.shape}")
+    if pts.ndim != 2 or pts.shape[1] != 3 or pts.shape[0] < 1:
+        raise ValueError(f"points3d must be (N >= 1, 3), got {pts.shape}")
+    N = pts.shape[0]
+    if obs.shape != (C, N, 2) or use.shape != (N, C):
+        raise ValueError(f"obs must be {(C, N, 2)} and use {(N, C)}, got {obs.shape} and {use.shape}")
+    if not (np.isfinite(pts).all() and np.isfinite(obs.transpose(1, 0, 2)[use]).all()):
+        raise ValueError("non-finite point or observation in use")
+    dev = torch.device("cuda", device)
+    ctx = _lib.Context.get(device)
+    obs_k = np.where(use.T[:, :, None], obs, 0.0)      # what nobody uses is never read: zero it anyway
+    x_d = torch.from_numpy(np.ascontiguousarray(pts)).to(dev)
+    obs_d = torch.from_numpy(np.ascontiguousarray(obs_k)).to(dev)
+    use_d = torch.from_numpy(np.ascontiguousarray(use, dtype=np.uint8)).to(dev)
+    res_d = torch.zeros((N, C, 2), dtype=torch.float64, device=dev) if return_residuals else None
+    cam_h = np.ascontiguousarray(cam)
+    info_h = np.zeros(8, dtype=np.float64)
+    rc = ctx.lib.mq_bundle_adjust_group(ctx.handle, C, N, fixed.ctypes.data, cam_h.ctypes.data, mask.ctypes.data,
+                                        _lib.ptr(x_d), _lib.ptr(obs_d), _lib.ptr(use_d), float(ftol), float(xtol),
+                                        int(max_iter), _lib.ptr(res_d), info_h.ctypes.data, _lib.stream_ptr(dev))
+    if rc == -2:
+        raise ValueError(ctx.lib.mq_last_error().decode())
+    _lib.check(rc, "mq_bundle_adjust_group")
+    info = {"cost0": float(info_h[0]), "cost": float(info_h[1]), "iterations": int(info_h[2]),
+            "stop": STOP_REASONS[int(info_h[3])], "accepted": int(info_h[4]), "lambda": float(info_h[5]),
+            "linearisations": int(info_h[6]), "n_free": int(info_h[7]), "n_points": N}
+    if return_residuals:
+        info["residuals"] = res_d.cpu().numpy()
+    return cam_h, x_d.cpu().numpy(), info

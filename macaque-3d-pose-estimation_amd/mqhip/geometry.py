@@ -137,6 +137,36 @@ class Camera:
         m[2, 2] = 1
         self.set_camera_matrix(m)
 
+    def get_params(self):
+        """cameras.py:279-288: [rvec, tvec, f, k1] (+ k2 with ``extra_dist``), f = (fx + fy) / 2."""
+        params = np.zeros(8 + bool(self.extra_dist), dtype=np.float64)
+        params[0:3] = self.get_rotation()
+        params[3:6] = self.get_translation()
+        params[6] = self.get_focal_length()
+        dist = self.get_distortions()
+        params[7] = dist[0]
+        if self.extra_dist:
+            params[8] = dist[1]
+        return params
+
+    def set_params(self, params):
+        """cameras.py:290-299 (:392-403, :518-529): fx = fy = f and the distortions replaced by zeros
+        (``n_dist`` of them: 5 for Camera, 4 for the other two) except k1 (and k2 with ``extra_dist``)."""
+        self.set_rotation(params[0:3])
+        self.set_translation(params[3:6])
+        self.set_focal_length(params[6])
+        dist = np.zeros(self.n_dist, dtype=np.float64)
+        dist[0] = params[7]
+        if self.extra_dist:
+            dist[1] = params[8]
+        self.set_distortions(dist)
+
+    def _group_fixed_row(self):
+        """What ``bundle_adjust`` does not move (mq_bundle_adjust_group's cam_fixed row): model, cx, cy."""
+        row = np.zeros(11)
+        row[0:3] = [self.model, self.matrix[0, 2], self.matrix[1, 2]]
+        return row
+
     def copy(self):
         import copy as _copy
         return _copy.deepcopy(self)
@@ -243,6 +273,15 @@ class OmnidirCamera(Camera):
         d = super().get_dict()
         d.update({"Omnidir": True, "xi": self.xi, "K": self.K, "D": self.D})
         return d
+
+    def _group_fixed_row(self):
+        """model, K00, K01, K02, K11, K12, xi, D[4]: ``project`` uses K, xi and D (cameras.py:509-516), which
+        ``set_params`` does not touch, so bundle adjustment refines an omnidir camera's extrinsics only."""
+        row = np.zeros(11)
+        row[0:7] = [self.model, self.K[0, 0], self.K[0, 1], self.K[0, 2], self.K[1, 1], self.K[1, 2],
+                    float(self.xi[0])]
+        row[7:11] = self.D[:4]
+        return row
 
     def param_row(self):
         row = np.zeros(24)
@@ -535,6 +574,129 @@ class CameraGroup:
         from .optim import triangulate_optim
         return triangulate_optim(self, points, init_ransac=init_ransac, init_progress=init_progress, **kwargs)
 
+    def bundle_adjust(self, p2ds, extra=None, loss='linear', threshold=50, ftol=1e-4, max_nfev=1000, weights=None,
+                      start_params=None, verbose=True):
+        """cameras.py:894-946 on the GPU: refine every camera's [rvec, tvec, f, k1(, k2)] and the N points on the
+        CxNx2 points ``p2ds`` (NaN = not seen), write the result back with ``set_params`` and return
+        ``average_error(p2ds)``.  The solve is ``mqhip.bundle.bundle_adjust_group``: a
+        Levenberg-Marquardt that stands in for the reference's ``least_squares(method='trf', x_scale='jac')``;
+        ``max_nfev`` maps to trial steps, ``weights`` is accepted and ignored (as in the reference), ``threshold``
+        only scales a robust loss.  ``self.last_bundle_info`` keeps the solver's info dict.
+
+        As in the reference, the residual is evaluated on the model ``set_params`` leaves (fx = fy = f, every
+        distortion but k1(, k2) zero), and every camera comes back rewritten that way.  An OmnidirCamera projects
+        with K, xi and D, which ``set_params`` does not touch: its f, k1, k2 columns have a zero Jacobian in the
+        reference too, so only its extrinsics are refined, while its ``matrix`` and ``dist`` still come back
+        rewritten by ``set_params``.
+
+        An observation counts when both of its coordinates are finite.  The reference masks coordinate by
+        coordinate (``~np.isnan(p2ds)``), so it would keep the finite coordinate of a half-NaN observation as one
+        residual; such an observation is dropped whole here.
+
+        Raises NotImplementedError for ``loss != 'linear'`` (the reference's own callers pass 'linear') and for
+        ``extra`` (board constraints need cv2 detections); ValueError for mixed ``extra_dist`` in the group and
+        for a non-finite start (a point fewer than 2 cameras see triangulates to NaN; scipy refuses it too)."""
+        from .bundle import N_GROUP_PARAMS, bundle_adjust_group, group_free_mask
+        p2ds = np.asarray(p2ds, dtype=np.float64)
+        assert p2ds.shape[0] == len(self.cameras), \
+            "Invalid points shape, first dim should be equal to" \
+            " number of cameras ({}), but shape is {}".format(len(self.cameras), p2ds.shape)
+        if loss != 'linear':
+            raise NotImplementedError(f"bundle_adjust(loss={loss!r}): only the linear loss is implemented")
+        if extra is not None:
+            raise NotImplementedError("bundle_adjust(extra=...): board constraints are not implemented")
+        extra_dist = {bool(c.extra_dist) for c in self.cameras}
+        if len(extra_dist) != 1:
+            raise ValueError("bundle_adjust: the cameras of a group must agree on extra_dist")
+        extra_dist = extra_dist.pop()
+        C, N = p2ds.shape[0], p2ds.shape[1]
+        n_cam_params = 8 + extra_dist
+        if start_params is not None:
+            x0 = np.asarray(start_params, dtype=np.float64).ravel()
+            if x0.size != C * n_cam_params + 3 * N:
+                raise ValueError(f"start_params must hold {C} x {n_cam_params} camera parameters and {N} points")
+        else:
+            x0 = np.hstack([np.hstack([cam.get_params() for cam in self.cameras]), self.triangulate(p2ds).ravel()])
+        if not np.isfinite(x0).all():
+            raise ValueError("bundle_adjust: the start is not finite (a point that fewer than 2 cameras see "
+                             "triangulates to NaN)")
+        params = np.zeros((C, N_GROUP_PARAMS))
+        params[:, :n_cam_params] = x0[:C * n_cam_params].reshape(C, n_cam_params)
+        fixed = np.stack([cam._group_fixed_row() for cam in self.cameras])
+        use = ~np.isnan(p2ds).any(axis=2).T
+        params, _, info = bundle_adjust_group(fixed, params, group_free_mask(fixed[:, 0], extra_dist),
+                                              x0[C * n_cam_params:].reshape(N, 3), p2ds, use, ftol=ftol,
+                                              max_iter=max_nfev, device=self.device)
+        self.last_bundle_info = info
+        if verbose:
+            print("bundle_adjust: cost {:.6e} -> {:.6e}, {} steps ({} accepted), stop: {}".format(
+                info["cost0"], info["cost"], info["iterations"], info["accepted"], info["stop"]))
+        for cam, row in zip(self.cameras, params):
+            cam.set_params(row[:n_cam_params])
+        self.invalidate()
+        return self.average_error(p2ds)
+
+    def _point_errors(self, p2ds):
+        """Triangulate ``p2ds`` and measure it: the mean reprojection error of every point, and the largest 15th
+        and the largest 75th percentile that ``get_error_dict`` finds over the camera pairs (0 with no pair)."""
+        p3ds = self.triangulate(p2ds)
+        per_point = self.reprojection_error(p3ds, p2ds, mean=True)
+        low = high = 0
+        for _, (p15, p75) in get_error_dict(self.reprojection_error(p3ds, p2ds, mean=False)).values():
+            low, high = max(low, p15), max(high, p75)
+        return per_point, low, high
+
+    def bundle_adjust_iter(self, p2ds, extra=None, n_iters=10, start_mu=15, end_mu=1, max_nfev=200, ftol=1e-4,
+                           n_samp_iter=100, n_samp_full=1000, error_threshold=0.3, verbose=False):
+        """cameras.py:786-892: bundle adjustment repeated on resampled inliers.  A point is an inlier while its
+        mean reprojection error is below a threshold that falls geometrically from ``start_mu`` to ``end_mu`` over
+        ``n_iters`` rounds, held between the largest 15th and the largest 75th percentile of the camera pairs'
+        errors.  A round whose median error is already below ``error_threshold`` ends the rounds.  Then, as in the
+        reference whether the rounds ended early or not, one solve on every inlier under max(75th percentile,
+        ``end_mu``) with max(200, ``max_nfev``) steps.  Returns the median error of the resampled points.
+
+        Triangulation, reprojection errors and the solves run on the GPU; percentiles, masks and
+        ``resample_points`` are host NumPy.  The subsets are drawn from numpy's global random stream in the
+        reference's order -- one ``n_samp_full`` subset up front, per round one ``n_samp_full`` subset and one
+        ``n_samp_iter`` subset of its inliers (drawn before the early exit is tested), one ``n_samp_full`` subset
+        for the last solve -- so ``np.random.seed`` reproduces the reference's subsets."""
+        everything = np.asarray(p2ds, dtype=np.float64)
+        assert everything.shape[0] == len(self.cameras), \
+            "Invalid points shape, first dim should be equal to" \
+            " number of cameras ({}), but shape is {}".format(len(self.cameras), everything.shape)
+        if extra is not None:
+            raise NotImplementedError("bundle_adjust_iter(extra=...): board constraints are not implemented")
+
+        def draw(points, n_samp):
+            return resample_points(points, None, n_samp=n_samp)[0]
+
+        median = self.average_error(draw(everything, n_samp_full), median=True)
+        if verbose:
+            print(f"bundle_adjust_iter: median error {median} at the start, {n_samp_iter} samples per camera pair")
+        for round_no, mu_wanted in enumerate(np.geomspace(start_mu, end_mu, n_iters)):
+            sample = draw(everything, n_samp_full)
+            per_point, low, high = self._point_errors(sample)
+            mu = max(min(high, mu_wanted), low)
+            inlier = per_point < mu
+            solve_on = draw(sample[:, inlier], n_samp_iter)
+            median = np.median(per_point)
+            if median < error_threshold:
+                break
+            if verbose:
+                print(f"round {round_no}: median error {median:.3f}, threshold {mu:.2f}, "
+                      f"{100 * np.mean(inlier):.1f} % inliers")
+            self.bundle_adjust(solve_on, None, loss='linear', ftol=ftol, max_nfev=max_nfev, verbose=verbose)
+
+        sample = draw(everything, n_samp_full)
+        per_point, low, high = self._point_errors(sample)
+        inlier = per_point < max(high, end_mu, low)
+        self.bundle_adjust(sample[:, inlier], None, loss='linear', ftol=ftol, max_nfev=max(200, max_nfev),
+                           verbose=verbose)
+        median = self.average_error(sample, median=True)
+        if verbose:
+            print(f"bundle_adjust_iter: median error {median} at the end")
+        return median
+
     def optim_points_jointlenfix(self, points, p3ds, joint_len, constraints=(), constraints_weak=(), scale_smooth=4,
                                  scale_length=2, scale_length_weak=0.5, reproj_error_threshold=15,
                                  reproj_loss='soft_l1', n_deriv_smooth=1, scores=None, verbose=False):
@@ -549,6 +711,61 @@ class CameraGroup:
                                  reproj_loss=reproj_loss, n_deriv_smooth=n_deriv_smooth, scores=scores,
                                  verbose=verbose, joint_len=joint_len, max_iter=14, max_nfev=15)
         return p3, joint_len
+
+
+# The helpers of bundle_adjust_iter (cameras.py:35-127), host NumPy.  A point counts as seen by a camera when its
+# first coordinate is not NaN, as in the reference.
+def _seen_by_pairs(points):
+    """(i, j, mask of the points cameras i and j both see) for every camera pair i < j of a CxNx2 array."""
+    seen = ~np.isnan(points[:, :, 0])
+    for i in range(len(seen)):
+        for j in range(i + 1, len(seen)):
+            yield i, j, seen[i] & seen[j]
+
+
+def get_error_dict(errors_full, min_points=10):
+    """{(i, j): (n, [p15, p75])} for every camera pair with n > ``min_points`` common points: the 15th and 75th
+    percentiles, over those points, of the mean of the two cameras' error norms.  errors_full is CxNx2, NaN where
+    a camera does not see a point."""
+    size = np.linalg.norm(errors_full, axis=2)
+    out = {}
+    for i, j, common in _seen_by_pairs(errors_full):
+        n = int(np.count_nonzero(common))
+        if n > min_points:
+            out[(i, j)] = (n, np.percentile((size[i, common] + size[j, common]) / 2, [15, 75]))
+    return out
+
+
+def check_errors(cgroup, imgp):
+    """``get_error_dict`` of a group's reprojection errors on its own triangulation of ``imgp``."""
+    return get_error_dict(cgroup.reprojection_error(cgroup.triangulate(imgp), imgp, mean=False))
+
+
+def subset_extra(extra, ixs):
+    """Board data restricted to the points ``ixs``: per-point arrays on axis 0, per-camera poses on axis 1."""
+    if extra is None:
+        return None
+    return {key: extra[key][:, ixs] if key in ('rvecs', 'tvecs') else extra[key][ixs]
+            for key in ('objp', 'ids', 'rvecs', 'tvecs')}
+
+
+def resample_points(imgp, extra=None, n_samp=25):
+    """A subset of the points that covers every camera pair: per pair up to ``n_samp`` of its common points, those
+    that more cameras see first; the union over the pairs, in index order.  Returns (imgp[:, chosen], the matching
+    subset of ``extra``).
+
+    Ties among equally seen points are broken at random: one ``np.random.random`` draw per pair that has common
+    points, in pair order, of that pair's number of common points -- the reference's use of numpy's global stream,
+    so ``np.random.seed`` reproduces its subsets."""
+    views = np.count_nonzero(~np.isnan(imgp[:, :, 0]), axis=0)
+    chosen = np.zeros(imgp.shape[1], dtype=bool)
+    for _, _, common in _seen_by_pairs(imgp):
+        candidates = np.flatnonzero(common)
+        if candidates.size:
+            rank = views[candidates] + np.random.random(size=candidates.shape)
+            chosen[candidates[np.argsort(rank)[::-1][:n_samp]]] = True
+    chosen = np.flatnonzero(chosen)
+    return imgp[:, chosen], subset_extra(extra, chosen)
 
 
 def _toml_ready(d):
