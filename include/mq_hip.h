@@ -738,6 +738,44 @@ int mq_bundle_adjust_group(mq_ctx* ctx, int n_cams, int n_points, const double* 
                            const uint8_t* free_mask, double* points3d, const double* obs, const uint8_t* use,
                            double ftol, double xtol, int max_iter, double* resid, double* info, void* stream);
 
+/* ---- Camera calibration from detected points (csrc/calib.hip): the fits the reference takes from OpenCV in
+ * calibrate_intrinsic (multicam_toolbox.py:74-116: cv2.calibrateCamera :96, cv2.omnidir.calibrate :100-111) and in
+ * get_extrinsic_from_cagekeypoints (:213-242: cv2.solvePnP :234).  A problem is one camera: 10 intrinsic slots
+ * and one pose (rvec, tvec) per view.  OpenCV is not a dependency; parity with it is not pinned.
+ *   model       : 0 omnidir -- slots fx, fy, s, cx, cy, xi, k1, k2, p1, p2 (cv2.omnidir.projectPoints);
+ *                 1 pinhole -- slots fx, fy, cx, cy, k1, k2, p1, p2, k3, unused (cv2.projectPoints)
+ *   view_prefix : HOST int32 (n_prob + 1): problem p owns views view_prefix[p] .. view_prefix[p + 1]; a problem
+ *                 may have no views
+ *   pt_prefix   : HOST int32 (n_views + 1): view v owns points pt_prefix[v] .. pt_prefix[v + 1], at least 4
+ *   obj, img    : device float64 (n_pts, 3) object points and (n_pts, 2) pixels
+ *
+ * mq_calib_init: closed-form starts.  Planar views (smallest eigenvalue of the object points' scatter matrix below
+ * 1e-3 of the middle one): Hartley-normalised DLT homography; with use_intrinsics = 0 Zhang's two constraints per
+ * view give fx, fy with the centre fixed at ((width - 1) / 2, (height - 1) / 2) and zero distortion (the omnidir
+ * start: fx, fy doubled, xi = 1), and K^-1 H gives each pose.  With use_intrinsics != 0 the given slots are kept,
+ * the pixels are normalised through them, and only poses are made; a non-planar view then takes a 3 x 4 DLT on
+ * at least 6 points.
+ *   intrinsics  : HOST float64 (n_prob, 10), in (use_intrinsics) / out;  poses : HOST float64 (n_views, 6), out
+ * Returns -2 (nothing written) for an argument error, a non-planar view without intrinsics or with fewer than 6
+ * points, a singular focal-length system, or a non-finite pose.
+ *
+ * mq_calibrate_views: Levenberg-Marquardt on the Schur complement of the 6 x 6 view blocks, Marquardt scaling,
+ * the whole iteration in one launch with one workgroup per problem; mq_bundle_adjust's step rules.
+ *   free_mask   : HOST uint8 (n_prob, 10): the intrinsic slots the solve may move; all zero is the pose-only
+ *                 problem (solvePnP).  Slot 9 of a pinhole problem must be 0.
+ *   ftol, xtol, max_iter : as mq_bundle_adjust (ftol = 0 disables the cost rule; max_iter = 0 only evaluates)
+ *   intrinsics, poses : HOST, in / out;  resid : device float64 (n_pts, 2) or NULL, projection - pixel at the result
+ *   info        : HOST float64 (n_prob, 8) in mq_bundle_adjust's layout; info[7] counts the problem's unknowns
+ *                 (free slots + 6 per view).  A problem without views keeps its slots: cost 0, stop reason 4.
+ * No floating-point atomics, no dependence between problems: the same bits on every call and in every batch.
+ * Both synchronise stream. */
+int mq_calib_init(mq_ctx* ctx, int model, int n_prob, const int* view_prefix, const int* pt_prefix,
+                  const double* obj, const double* img, int width, int height, int use_intrinsics,
+                  double* intrinsics, double* poses, void* stream);
+int mq_calibrate_views(mq_ctx* ctx, int model, int n_prob, const int* view_prefix, const int* pt_prefix,
+                       const double* obj, const double* img, const uint8_t* free_mask, double ftol, double xtol,
+                       int max_iter, double* intrinsics, double* poses, double* resid, double* info, void* stream);
+
 /* ---- Motion-JPEG frames (csrc/jpeg.hip): a baseline JPEG encoder for the overlay frames, so that only the
  * compressed stream leaves the device.  tests/jpeg_ref.py is the numpy restatement, equal byte for byte: integer
  * arithmetic only, no atomics on global memory, the same bits on every call.

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "bundle.hpp"
+#include "calib.hpp"
 #include "candidates.hpp"
 #include "cmc.hpp"
 #include "geometry.hpp"
@@ -89,6 +90,7 @@ struct mq_ctx {
   DevBuf det_ws;    // detector post-processing (sort, NMS masks)
   DevBuf dlt_ws;    // mq_triangulate_dlt: undistorted points
   DevBuf ba_ws;     // mq_bundle_adjust: per-observation blocks, partials, trial points
+  DevBuf calib_ws;  // mq_calib_init / mq_calibrate_views: problem description, per-view blocks, trial poses
   DevBuf jpeg_ws;   // mq_jpeg_encode: coefficients, per-interval slots, lengths, offsets
   DevBuf jpeg_dec_ws;  // mq_jpeg_decode: coefficients, component planes, interval ends
   mq::SiftWs* sift_ws = nullptr;  // SIFT pyramid + candidates of the stage entry points (mq_sift_*)
@@ -248,6 +250,7 @@ int mq_destroy(mq_ctx* ctx) {
   ctx->assoc_ws.release();
   ctx->dlt_ws.release();
   ctx->ba_ws.release();
+  ctx->calib_ws.release();
   ctx->jpeg_ws.release();
   ctx->jpeg_dec_ws.release();
   ctx->det_ws.release();
@@ -1906,6 +1909,91 @@ int mq_bundle_adjust_group(mq_ctx* ctx, int n_cams, int n_points, const double* 
   const int rc = mq::bundle_adjust_group(n_cams, n_points, cam_params, cam_fixed, free_mask, points3d, obs, use, ftol,
                                          xtol, max_iter, resid, info, ctx->ba_ws.p, (hipStream_t)stream);
   if (rc != 0) return fail("mq_bundle_adjust_group: solver failed (" + std::to_string(rc) + ")", rc == -5 ? -5 : -6);
+  return 0;
+}
+
+// ----------------------------------------------------------------------------- view calibration
+namespace {
+
+// the problem description both calibration entry points share; 0, or -2 with the error set
+int calib_check(const char* who, int model, int n_prob, const int* view_prefix, const int* pt_prefix,
+                const double* obj, const double* img, int* n_views, int* n_pts) {
+  const std::string w(who);
+  if (model != 0 && model != 1) return fail(w + ": model must be 0 (omnidir) or 1 (pinhole)", -2);
+  if (n_prob < 1 || n_prob > (1 << 16)) return fail(w + ": n_prob must be in [1, 2^16]", -2);
+  if (!view_prefix || !pt_prefix || !obj || !img) return fail(w + ": null argument");
+  if (view_prefix[0] != 0) return fail(w + ": view_prefix must start at 0", -2);
+  for (int p = 0; p < n_prob; ++p)
+    if (view_prefix[p + 1] < view_prefix[p]) return fail(w + ": view_prefix must not fall", -2);
+  const int V = view_prefix[n_prob];
+  if (V > (1 << 22)) return fail(w + ": more than 2^22 views", -2);
+  if (pt_prefix[0] != 0) return fail(w + ": pt_prefix must start at 0", -2);
+  for (int v = 0; v < V; ++v) {
+    const int n = pt_prefix[v + 1] - pt_prefix[v];
+    if (n < 4) return fail(w + ": view " + std::to_string(v) + " has fewer than 4 points", -2);
+    if (pt_prefix[v + 1] > (1 << 26)) return fail(w + ": more than 2^26 points", -2);
+  }
+  *n_views = V;
+  *n_pts = pt_prefix[V];
+  return 0;
+}
+
+}  // namespace
+
+int mq_calib_init(mq_ctx* ctx, int model, int n_prob, const int* view_prefix, const int* pt_prefix,
+                  const double* obj, const double* img, int width, int height, int use_intrinsics,
+                  double* intrinsics, double* poses, void* stream) {
+  if (!ctx) return fail("mq_calib_init: null ctx");
+  int V = 0, N = 0;
+  const int bad = calib_check("mq_calib_init", model, n_prob, view_prefix, pt_prefix, obj, img, &V, &N);
+  if (bad) return bad;
+  if (!intrinsics || !poses) return fail("mq_calib_init: null argument");
+  if (width < 1 || height < 1) return fail("mq_calib_init: bad image size", -2);
+  if (use_intrinsics)
+    for (int k = 0; k < n_prob * mq::CAL_NI_API; ++k)
+      if (!std::isfinite(intrinsics[k])) return fail("mq_calib_init: non-finite intrinsic", -2);
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (ctx->calib_ws.ensure(mq::calib_workspace_bytes(n_prob, V, N)))
+    return fail("mq_calib_init: out of device memory", -5);
+  int where = -1;
+  const int rc = mq::calib_init(model, n_prob, V, N, view_prefix, pt_prefix, obj, img, width, height,
+                                use_intrinsics != 0, intrinsics, poses, &where, ctx->calib_ws.p, (hipStream_t)stream);
+  switch (rc) {
+    case 0: return 0;
+    case mq::CAL_INIT_NONPLANAR:
+      return fail("mq_calib_init: view " + std::to_string(where) + " is not planar: the intrinsic start needs planar targets", -2);
+    case mq::CAL_INIT_SINGULAR:
+      return fail("mq_calib_init: problem " + std::to_string(where) + ": the focal-length system of the views' homographies is singular (every view fronto-parallel?)", -2);
+    case mq::CAL_INIT_FEW:
+      return fail("mq_calib_init: view " + std::to_string(where) + " is not planar and has fewer than 6 points", -2);
+    case mq::CAL_INIT_POSE:
+      return fail("mq_calib_init: view " + std::to_string(where) + ": degenerate points, no finite pose", -2);
+    default: return fail("mq_calib_init: failed (" + std::to_string(rc) + ")", rc == -5 ? -5 : -6);
+  }
+}
+
+int mq_calibrate_views(mq_ctx* ctx, int model, int n_prob, const int* view_prefix, const int* pt_prefix,
+                       const double* obj, const double* img, const uint8_t* free_mask, double ftol, double xtol,
+                       int max_iter, double* intrinsics, double* poses, double* resid, double* info, void* stream) {
+  if (!ctx) return fail("mq_calibrate_views: null ctx");
+  int V = 0, N = 0;
+  const int bad = calib_check("mq_calibrate_views", model, n_prob, view_prefix, pt_prefix, obj, img, &V, &N);
+  if (bad) return bad;
+  if (!free_mask || !intrinsics || !poses || !info) return fail("mq_calibrate_views: null argument");
+  if (!(ftol >= 0.0) || !(xtol >= 0.0) || max_iter < 0) return fail("mq_calibrate_views: bad tolerance or max_iter", -2);
+  for (int k = 0; k < n_prob * mq::CAL_NI_API; ++k)
+    if (!std::isfinite(intrinsics[k])) return fail("mq_calibrate_views: non-finite intrinsic", -2);
+  for (int k = 0; k < V * 6; ++k)
+    if (!std::isfinite(poses[k])) return fail("mq_calibrate_views: non-finite pose", -2);
+  if (model == 1)
+    for (int p = 0; p < n_prob; ++p)
+      if (free_mask[p * mq::CAL_NI_API + 9]) return fail("mq_calibrate_views: slot 9 of a pinhole problem is unused and must be frozen", -2);
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (ctx->calib_ws.ensure(mq::calib_workspace_bytes(n_prob, V, N)))
+    return fail("mq_calibrate_views: out of device memory", -5);
+  const int rc = mq::calibrate_views(model, n_prob, V, N, view_prefix, pt_prefix, obj, img, free_mask, ftol, xtol,
+                                     max_iter, intrinsics, poses, resid, info, ctx->calib_ws.p, (hipStream_t)stream);
+  if (rc != 0) return fail("mq_calibrate_views: solver failed (" + std::to_string(rc) + ")", rc == -5 ? -5 : -6);
   return 0;
 }
 

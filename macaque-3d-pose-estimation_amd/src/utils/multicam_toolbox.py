@@ -1,5 +1,4 @@
-"""multicam_toolbox point functions used by steps 2-3 (row a17) and the rig calibration refinement
-(``optimize_extrinsic``, ``optimize_all_camera_params``), backed by libmq_hip.
+"""multicam_toolbox point functions used by steps 2-3 (row a17) and the rig calibration, backed by libmq_hip.
 
 ``undistortPoints(config_path, pos_2d, omnidir, camparam)`` and
 ``triangulatePoints(config_path, pos_2d_undist, frame_use, use_optim_extrin, camparam)``
@@ -8,9 +7,13 @@ dict path is supported (``camera_id``, ``K``, ``xi``, ``D`` and ``pmat`` = [R|t]
 per camera); the h5 path needs h5py, which this image lacks, and raises.
 Only omnidir undistortion is on the path (step2/3 call it with omnidir=True).
 
-``optimize_extrinsic`` / ``optimize_all_camera_params`` (:488-824) produce the refined calibration the steps read
-(``cam_extrinsic_optim.h5``); their solve runs in ``mqhip.bundle`` (csrc/bundle.hip).  ``fix_extrinsic_optim``
-(:942-974) is not provided: it edits ``cam_extrinsic_optim.h5`` in place through h5py's append mode and
+The calibration chain from detected points onwards: ``calibrate_intrinsic`` (:74-116, chessboard corners ->
+``cam_intrinsic.h5``'s ``mtx``, ``dist``, ``K``, ``xi``, ``D``) and ``get_extrinsic_from_cagekeypoints`` (:213-242,
+cage annotations -> ``cam_extrinsic.h5``'s ``rvec``, ``tvec``) fit cameras to points in ``mqhip.calib``
+(csrc/calib.hip); ``optimize_extrinsic`` / ``optimize_all_camera_params`` (:488-824) refine the rig on a marker
+trace in ``mqhip.bundle`` (csrc/bundle.hip) and produce the calibration the steps read.  What needs images stays
+out: chessboard / ArUco detection and the labelling GUI (:22-72, :118-211, :244-391).  ``fix_extrinsic_optim``
+(:942-974) is not provided either: it edits ``cam_extrinsic_optim.h5`` in place through h5py's append mode and
 ``applytransform``, which is file surgery rather than array work.
 """
 import os
@@ -60,6 +63,162 @@ def triangulatePoints(config_path, pos_2d_undist, frame_use, use_optim_extrin=Tr
     g = CameraGroup(cams, device=device)
     und = np.stack([np.asarray(u, dtype=np.float64).reshape(-1, 2) for u in pos_2d_undist[:C]])
     return triangulate_pinv(g, und, np.asarray(frame_use, dtype=bool))
+
+
+# ----------------------------------------------------------------------------- calibration from detected points
+def _camera_ids(config_path):
+    import yaml
+    with open(config_path, 'r') as f:
+        return yaml.safe_load(f)
+
+
+def _h5_or_raise():
+    try:
+        import h5py  # absent in this image; the reference's files are read and written only when it imports
+    except ImportError:
+        _require_camparam(None)
+    return h5py
+
+
+def calibrate_intrinsic(config_path, mtx_init=None, dist_init=None, *, chessboard_points=None, img_size=None,
+                        device: int = 0, return_info=False):
+    """multicam_toolbox.calibrate_intrinsic (:74-116) on the GPU.  Per camera id, from the detected chessboard
+    corners ``imp`` (V, 54, 1, 2) and their board coordinates ``objp`` (V, 54, 3): one pinhole fit gives ``mtx``
+    (3, 3) and ``dist`` (1, 5) (``cv2.calibrateCamera``, flags 0, :88) and one omnidir fit gives ``K`` (3, 3), ``xi``
+    (1, 1), ``D`` (1, 4) (``cv2.omnidir.calibrate`` with CALIB_USE_GUESS + CALIB_FIX_SKEW + CALIB_FIX_CENTER and
+    criteria (200, 1e-8), :100-111).  All cameras go through one ``mqhip.calib.calibrate_views`` call per model.
+
+    ``chessboard_points`` = {camera id: {'imp': ..., 'objp': ...}} and ``img_size`` = (width, height) keep files out
+    of it.  Otherwise h5py must import: ``camera_id`` and ``img_size`` come from ``config_path``,
+    ``chessboard_points.h5`` next to it is read and ``cam_intrinsic.h5`` is written (:80-116).
+
+    Returns a camparam-style dict that ``get_extrinsic_from_cagekeypoints``, ``optimize_extrinsic`` and the
+    calibration.toml writer take as it is: ``camera_id``, ``mtx``, ``dist``, ``K``, ``xi``, ``D`` per camera, plus
+    ``rms`` (the omnidir fit's, px) and ``rms_pinhole``, the omnidir fit's per-view poses ``view_rvecs`` /
+    ``view_tvecs`` (V arrays (3, 1) per camera; ``rvecs`` / ``tvecs`` stay free for the rig's extrinsics) and
+    ``idx``, every view (this fit drops none).  With ``return_info`` also the solver's info dicts.
+
+    Not pinned against OpenCV, which is not a dependency: the start (Zhang's closed form
+    with the centre at ((w - 1) / 2, (h - 1) / 2); the omnidir start doubles fx, fy and sets xi = 1), the frozen
+    omnidir centre (w / 2 - 0.5, h / 2 - 0.5), and ``mtx_init`` / ``dist_init``: here they replace the closed-form
+    focal length and the zero distortion as the pinhole start; whether cv2 with flags 0 honours them is not
+    known."""
+    from mqhip import calib
+    from_h5 = chessboard_points is None
+    if from_h5:
+        h5py = _h5_or_raise()
+        cfg = _camera_ids(config_path)
+        ID = list(cfg['camera_id'])
+        img_size = img_size or cfg['img_size']
+        base = os.path.dirname(config_path)
+        chessboard_points = {}
+        with h5py.File(base + '/chessboard_points.h5', mode='r') as f:
+            for i in ID:
+                chessboard_points[i] = {'imp': f[str(i)]['imp'][()], 'objp': f[str(i)]['objp'][()]}
+    else:
+        ID = list(chessboard_points.keys())
+        if img_size is None:
+            raise ValueError("img_size = (width, height) is needed with chessboard_points")
+    if not ID:
+        raise ValueError("no camera to calibrate")
+    obj, img, vpp = [], [], []
+    for i in ID:
+        imp = np.asarray(chessboard_points[i]['imp'], dtype=np.float64)
+        objp = np.asarray(chessboard_points[i]['objp'], dtype=np.float64)
+        if imp.ndim < 3 or imp.shape[-1] != 2 or objp.ndim != 3 or objp.shape[-1] != 3:
+            raise ValueError(f"camera {i}: imp must be (V, n, 1, 2) and objp (V, n, 3), got {imp.shape} and {objp.shape}")
+        imp = imp.reshape(imp.shape[0], -1, 2)
+        if imp.shape[:2] != objp.shape[:2]:
+            raise ValueError(f"camera {i}: {imp.shape[:2]} image points for {objp.shape[:2]} object points")
+        vpp.append(imp.shape[0])
+        obj.extend(objp)
+        img.extend(imp)
+    size = (int(img_size[0]), int(img_size[1]))
+    k_init = None
+    if mtx_init is not None:
+        k_init = np.tile(calib.pinhole_slots(mtx_init, np.zeros(5) if dist_init is None else dist_init), (len(ID), 1))
+    elif dist_init is not None:
+        raise ValueError("dist_init needs mtx_init")
+    kp, _, rms_p, info_p = calib.calibrate_views(calib.MODEL_PINHOLE, obj, img, vpp, size, intrinsics0=k_init,
+                                                device=device)
+    ko, poses, rms_o, info_o = calib.calibrate_views(calib.MODEL_OMNIDIR, obj, img, vpp, size, device=device)
+    out = {'camera_id': ID, 'mtx': [], 'dist': [], 'K': [], 'xi': [], 'D': [], 'rms': [float(r) for r in rms_o],
+           'rms_pinhole': [float(r) for r in rms_p], 'view_rvecs': [], 'view_tvecs': [], 'idx': []}
+    at = 0
+    for c, V in enumerate(vpp):
+        mtx, dist = calib.pinhole_from_slots(kp[c])
+        K, xi, D = calib.omnidir_from_slots(ko[c])
+        for key, val in (('mtx', mtx), ('dist', dist), ('K', K), ('xi', xi), ('D', D)):
+            out[key].append(val)
+        out['view_rvecs'].append([poses[v, :3].reshape(3, 1).copy() for v in range(at, at + V)])
+        out['view_tvecs'].append([poses[v, 3:].reshape(3, 1).copy() for v in range(at, at + V)])
+        out['idx'].append(np.arange(V, dtype=np.int32)[np.newaxis, :])
+        at += V
+    if from_h5:
+        with h5py.File(base + '/cam_intrinsic.h5', mode='w') as f:
+            for c, i in enumerate(ID):
+                for key in ('mtx', 'dist', 'K', 'xi', 'D'):
+                    f.create_dataset('/' + str(i) + '/' + key, data=out[key][c])
+    return (out, {'pinhole': info_p, 'omnidir': info_o}) if return_info else out
+
+
+def get_extrinsic_from_cagekeypoints(config_path, *, cagepoints=None, camparam=None, device: int = 0):
+    """multicam_toolbox.get_extrinsic_from_cagekeypoints (:213-242) on the GPU: each camera's pose in the cage's
+    frame from its annotated cage keypoints, ``cv2.solvePnP(objp, imgp, mtx, dist)`` (:234) as the pose-only case of
+    ``mqhip.calib.calibrate_views``, all cameras in one call.
+
+    ``cagepoints`` = {camera id: (n, 6) rows of flag, u, v, X, Y, Z}: rows with flag > 0 are used, the pixels are
+    annotated on the 640-wide preview and scaled by 2048 / 640 (:229-232).  ``camparam`` carries ``camera_id``,
+    ``mtx`` and ``dist`` (``calibrate_intrinsic``'s result).  Otherwise h5py must import:
+    ``cagepoints_annotation.h5`` and ``cam_intrinsic.h5`` next to ``config_path`` are read and ``cam_extrinsic.h5``
+    is written with ``rvec`` (3, 1), ``tvec`` (3, 1) (:236-237).  Prints the camera positions as :239-242 does and
+    returns the camparam with ``rvecs`` / ``tvecs`` (3, 1) per camera added.
+
+    A planar set of keypoints needs 4 points, any other 6 (``ValueError`` otherwise); the planarity rule is
+    cv2.solvePnP's as recalled, not pinned."""
+    from mqhip import calib
+    from mqhip.geometry import rodrigues
+    from_h5 = cagepoints is None or camparam is None
+    if from_h5:
+        h5py = _h5_or_raise()
+        base = os.path.dirname(config_path)
+        if camparam is None:
+            ID = list(_camera_ids(config_path)['camera_id'])
+            camparam = {'camera_id': ID, 'mtx': [], 'dist': []}
+            with h5py.File(base + '/cam_intrinsic.h5', mode='r') as f:
+                for i in ID:
+                    camparam['mtx'].append(np.asarray(f[str(i)]['mtx'][()], dtype=np.float64))
+                    camparam['dist'].append(np.asarray(f[str(i)]['dist'][()], dtype=np.float64))
+        if cagepoints is None:
+            with h5py.File(base + '/cagepoints_annotation.h5', mode='r') as f:
+                cagepoints = {i: f[str(i)][()] for i in camparam['camera_id']}
+    ID = list(camparam['camera_id'])
+    if 'mtx' not in camparam or 'dist' not in camparam:
+        raise ValueError("camparam needs mtx and dist (calibrate_intrinsic's result)")
+    obj, img, k = [], [], []
+    for c, i in enumerate(ID):
+        cp = np.asarray(cagepoints[i], dtype=np.float64)
+        if cp.ndim != 2 or cp.shape[1] != 6:
+            raise ValueError(f"camera {i}: cage points must be (n, 6) rows of flag, u, v, X, Y, Z, got {cp.shape}")
+        cp = cp[cp[:, 0] > 0, 1:]
+        img.append(cp[:, 0:2] * 2048 / 640)
+        obj.append(cp[:, 2:])
+        k.append(calib.pinhole_slots(camparam['mtx'][c], camparam['dist'][c]))
+    _, poses, _, _ = calib.calibrate_views(calib.MODEL_PINHOLE, obj, img, [1] * len(ID), (2048, 1536),
+                                           free_mask=np.zeros(calib.N_SLOTS), intrinsics0=np.stack(k),
+                                           max_iter=100, xtol=1e-12, device=device)
+    out = {key: (list(v) if isinstance(v, (list, tuple)) else v) for key, v in camparam.items()}
+    out['rvecs'] = [poses[c, :3].reshape(3, 1).copy() for c in range(len(ID))]
+    out['tvecs'] = [poses[c, 3:].reshape(3, 1).copy() for c in range(len(ID))]
+    if from_h5:
+        with h5py.File(base + '/cam_extrinsic.h5', mode='w') as f:
+            for c, i in enumerate(ID):
+                f.create_dataset('/' + str(i) + '/rvec', data=out['rvecs'][c])
+                f.create_dataset('/' + str(i) + '/tvec', data=out['tvecs'][c])
+    for c, i in enumerate(ID):
+        print('3D pos of camera ' + str(i))
+        print(-rodrigues(poses[c, :3]).T @ out['tvecs'][c])
+    return out
 
 
 # ----------------------------------------------------------------------------- rig calibration refinement
