@@ -23,28 +23,35 @@
 //     fixed order, so every workgroup holds the same scalars bit for bit and no launch waits on another
 //     workgroup.  The host checks the per-animal done flags every few iterations;
 //   * the trust-region logic (2x2 subproblem, radius, termination) runs on the host from the partials.
+//
+// What scipy's algorithm says, apart from this problem's rows, lives in two headers that also compile for a plain
+// host compiler (tests/trf_core_check.cpp runs them on the CPU): lsmr's scalar state, start, recurrences and stop
+// test and the fixed-order workgroup reductions are lsmr_dev.hpp; the loop's per-animal state and steps
+// (mq::TrfAnimal) and the 2-D subproblem are trf_host.hpp.  This file owns the problem:
+// the residual, J v, J^T u and n-space kernels, the buffers, the lsmr launch scheme (one recurrence lane per
+// workgroup, a captured graph of iterations, host-mapped partials) and the driver that sums the partials.
 #include <algorithm>
 #include <cstdio>
 #include <cmath>
 #include <cstring>
 #include <initializer_list>
-#include <limits>
 #include <vector>
 
 #include "camera.hpp"
 #include "common.hpp"
+#include "lsmr_dev.hpp"
 #include "optim_dev.hpp"
 #include "trf_host.hpp"
 
 namespace mq {
 namespace {
 
-constexpr int TRF_THREADS = 256;
+constexpr int TRF_THREADS = LSMR_THREADS;
 constexpr int TRF_FB = 4;  // frames per workgroup (at most; fewer when a block's rows would not fit in LDS)
 // (5 measured slower on config 4: 23.1 vs 20.9 ms for 240 instead of 300 workgroups; profiles/r06k_*)
 constexpr int TRF_MAXJ = 32, TRF_MAXL = 64, TRF_MAXN = 3;
 static_assert(TRF_FB * TRF_MAXJ * 3 <= 2 * TRF_THREADS, "a block's parameters: at most two per thread");
-constexpr int TRF_NS = 24;  // lsmr state doubles per slot
+constexpr int TRF_NS = LSMR_NS;  // lsmr state doubles per slot
 
 // -DTRF_PROFILE builds (tools only, never the shipped library): wall-clock time per phase of the two lsmr
 // kernels, block TRF_PROFILE_BLOCK (default 0) of animal 0, summed over launches and printed at the end of
@@ -105,60 +112,6 @@ struct TrfBufs {
   double* lctl;   // [B][4]: damp, normb, maxiter, final lsmr itn
   double* coef;   // [B][4]
 };
-
-// Sum over the workgroup; every thread returns the same bits (xor butterflies add the same two values,
-// commuted, and the wave sums combine in one fixed order).
-__device__ __forceinline__ double block_sum_all(double v, double* red) {
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const double s = (red[0] + red[1]) + (red[2] + red[3]);
-  __syncthreads();
-  return s;
-}
-
-__device__ __forceinline__ double block_max_all(double v, double* red) {
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) v = fmax(v, __shfl_xor(v, m));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const double s = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-  __syncthreads();
-  return s;
-}
-
-// sum_i p[i * stride] over i < count, the same value in every thread of every workgroup that asks
-__device__ __forceinline__ double reduce_parts(const double* __restrict__ p, int count, int stride, double* red) {
-  double v = 0.0;
-  for (int i = threadIdx.x; i < count; i += TRF_THREADS) v += p[(size_t)i * stride];
-  return block_sum_all(v, red);
-}
-
-// scipy.sparse.linalg._isolve.lsqr._sym_ortho (np.sign(0) = 0)
-__device__ __forceinline__ double sgn0(double a) { return a > 0 ? 1.0 : (a < 0 ? -1.0 : 0.0); }
-__device__ __forceinline__ void sym_ortho(double a, double b, double& c, double& s, double& r) {
-  if (b == 0) {
-    c = sgn0(a);
-    s = 0;
-    r = fabs(a);
-  } else if (a == 0) {
-    c = 0;
-    s = sgn0(b);
-    r = fabs(b);
-  } else if (fabs(b) > fabs(a)) {
-    const double tau = a / b;
-    s = sgn0(b) / sqrt(1 + tau * tau);
-    c = s * tau;
-    r = b / s;
-  } else {
-    const double tau = b / a;
-    c = sgn0(a) / sqrt(1 + tau * tau);
-    s = c * tau;
-    r = a / c;
-  }
-}
-
 
 // Global -> LDS staging with every load of a thread issued before its LDS stores (a plain copy loop waits on
 // each load before the next iteration's: one memory round trip per element a thread copies).  stage16: 16-B
@@ -287,14 +240,6 @@ __device__ __forceinline__ int trf_frame_of(int i, int per) {
   for (int k = 1; k < TRF_FB; ++k) fl += i >= k * per;
   return fl;
 }
-
-// lsmr state slot
-enum {
-  S_ALPHABAR, S_RHO, S_RHOBAR, S_CBAR, S_SBAR, S_ZETABAR, S_ZETA, S_BETADD, S_BETAD, S_RHODOLD, S_TAUTILDEOLD,
-  S_THETATILDE, S_D, S_NORMA2, S_MAXRBAR, S_MINRBAR, S_ITN, S_NORMR, S_NORMAR, S_NORMA, S_CONDA,
-  S_CHAT, S_SHAT, S_ALPHAHAT  // sym_ortho(alphabar, damp) of the next iteration (depends on neither norm)
-};
-static_assert(S_ALPHAHAT < TRF_NS, "lsmr state slot");
 
 // ---------------------------------------------------------------------------------------------------------
 // Residuals (and, mode 1, the Jacobian) at x for the block's frames.  fout: m vector [B][F][MR]:
@@ -685,93 +630,6 @@ __global__ void __launch_bounds__(TRF_THREADS) trf_jt_kernel(TrfDims D, TrfBufs 
 // of iteration k - 2 (lsmr.py:413-441, with ||x_{k-2}||: when it passes x_{k-2} is the answer and nothing more
 // runs), then iteration k - 1's recurrences (:301-410) and the hbar / x / h updates; then u_k = J v_{k-1} -
 // alpha_{k-1} u_{k-1} for the block's rows.
-__device__ __forceinline__ void lsmr_recurrence(double* S, double alpha, double beta, double damp, double& chb,
-                                                double& cx, double& ch) {
-  // (lsmr.py:305's rotation of alphabar and damp was computed with the previous iteration's recurrences, off
-  // the chain that waits on this iteration's norms)
-  const double chat = S[S_CHAT], shat = S[S_SHAT], alphahat = S[S_ALPHAHAT];
-  const double rhoold = S[S_RHO];
-  double c, s, rho;
-  sym_ortho(alphahat, beta, c, s, rho);
-  const double thetanew = s * alpha;
-  S[S_ALPHABAR] = c * alpha;
-  sym_ortho(S[S_ALPHABAR], damp, S[S_CHAT], S[S_SHAT], S[S_ALPHAHAT]);
-  const double rhobarold = S[S_RHOBAR];
-  const double zetaold = S[S_ZETA];
-  const double thetabar = S[S_SBAR] * rho;
-  const double rhotemp = S[S_CBAR] * rho;
-  double cbar, sbar, rhobar;
-  sym_ortho(S[S_CBAR] * rho, thetanew, cbar, sbar, rhobar);
-  const double zeta = cbar * S[S_ZETABAR];
-  const double zetabar = -sbar * S[S_ZETABAR];
-  chb = -(thetabar * rho / (rhoold * rhobarold));
-  cx = zeta / (rho * rhobar);
-  ch = -(thetanew / rho);
-  const double betaacute = chat * S[S_BETADD];
-  const double betacheck = -shat * S[S_BETADD];
-  const double betahat = c * betaacute;
-  const double betadd = -s * betaacute;
-  const double thetatildeold = S[S_THETATILDE];
-  double ctildeold, stildeold, rhotildeold;
-  sym_ortho(S[S_RHODOLD], thetabar, ctildeold, stildeold, rhotildeold);
-  const double thetatilde = stildeold * rhobar;
-  const double rhodold = ctildeold * rhobar;
-  const double betad = -stildeold * S[S_BETAD] + ctildeold * betahat;
-  const double tautildeold = (zetaold - thetatildeold * S[S_TAUTILDEOLD]) / rhotildeold;
-  const double taud = (zeta - thetatilde * tautildeold) / rhodold;
-  const double d = S[S_D] + betacheck * betacheck;
-  const double bt = betad - taud;
-  const double normr = sqrt(d + bt * bt + betadd * betadd);
-  double normA2 = S[S_NORMA2] + beta * beta;
-  const double normA = sqrt(normA2);
-  normA2 = normA2 + alpha * alpha;
-  const double itn = S[S_ITN] + 1;
-  const double maxrbar = fmax(S[S_MAXRBAR], rhobarold);
-  const double minrbar = itn > 1 ? fmin(S[S_MINRBAR], rhobarold) : S[S_MINRBAR];
-  const double condA = fmax(maxrbar, rhotemp) / fmin(minrbar, rhotemp);
-  S[S_RHO] = rho;
-  S[S_RHOBAR] = rhobar;
-  S[S_CBAR] = cbar;
-  S[S_SBAR] = sbar;
-  S[S_ZETABAR] = zetabar;
-  S[S_ZETA] = zeta;
-  S[S_BETADD] = betadd;
-  S[S_BETAD] = betad;
-  S[S_RHODOLD] = rhodold;
-  S[S_TAUTILDEOLD] = tautildeold;
-  S[S_THETATILDE] = thetatilde;
-  S[S_D] = d;
-  S[S_NORMA2] = normA2;
-  S[S_MAXRBAR] = maxrbar;
-  S[S_MINRBAR] = minrbar;
-  S[S_ITN] = itn;
-  S[S_NORMR] = normr;
-  S[S_NORMAR] = fabs(zetabar);
-  S[S_NORMA] = normA;
-  S[S_CONDA] = condA;
-}
-
-// the stop test of lsmr.py:413-441 from a state slot and ||x||; 0 = go on
-__device__ __forceinline__ int lsmr_istop(const TrfDims& D, const double* S, double normx, double normb,
-                                          double maxiter) {
-  const double normr = S[S_NORMR], normar = S[S_NORMAR], normA = S[S_NORMA], condA = S[S_CONDA];
-  const double itn = S[S_ITN];
-  const double test1 = normr / normb;
-  const double test2 = (normA * normr) != 0 ? normar / (normA * normr) : INFINITY;
-  const double test3 = 1 / condA;
-  const double t1 = test1 / (1 + normA * normx / normb);
-  const double rtol = D.btol + D.atol * normA * normx / normb;
-  int istop = 0;
-  if (itn >= maxiter) istop = 7;
-  if (1 + test3 <= 1) istop = 6;
-  if (1 + test2 <= 1) istop = 5;
-  if (1 + t1 <= 1) istop = 4;
-  if (test3 <= D.ctol) istop = 3;
-  if (test2 <= D.atol) istop = 2;
-  if (test1 <= rtol) istop = 1;
-  return istop;
-}
-
 template <bool FIRST>
 __global__ void __launch_bounds__(TRF_THREADS) trf_lsmr1_kernel(TrfDims D, TrfBufs Bf, int par) {
   TRF_PROF_BEGIN();
@@ -867,29 +725,17 @@ __global__ void __launch_bounds__(TRF_THREADS) trf_lsmr1_kernel(TrfDims D, TrfBu
   const int MW = FIRST ? TRF_THREADS : RT;
   if (t == RT) {
     double S[TRF_NS];
-#pragma unroll
-    for (int i = 0; i < TRF_NS; ++i) S[i] = FIRST ? 0.0 : sS[i];
     double chb = 0.0, cx = 0.0, ch = 0.0;
     int istop = 0;
     if (FIRST) {
-      S[S_ZETABAR] = alpha * beta;
-      S[S_ALPHABAR] = alpha;
-      sym_ortho(alpha, damp, S[S_CHAT], S[S_SHAT], S[S_ALPHAHAT]);
-      S[S_RHO] = 1;
-      S[S_RHOBAR] = 1;
-      S[S_CBAR] = 1;
-      S[S_SBAR] = 0;
-      S[S_BETADD] = beta;
-      S[S_RHODOLD] = 1;
-      S[S_NORMA2] = alpha * alpha;
-      S[S_MINRBAR] = 1e+100;
-      S[S_ITN] = 0;
-      if (!(alpha * beta != 0)) istop = 8;  // normar == 0 (or normb == 0): x = 0 (lsmr.py:247-256)
+      if (lsmr_start(S, alpha, beta, damp)) istop = 8;  // x = 0
     } else {
+#pragma unroll
+      for (int i = 0; i < TRF_NS; ++i) S[i] = sS[i];
       // the test and the recurrences side by side (independent chains; the recurrence's results are dropped
       // when the test stops the run)
       const double itn0 = S[S_ITN];
-      if (itn0 >= 1) istop = lsmr_istop(D, S, sqrt(px), normb, maxiter);
+      if (itn0 >= 1) istop = lsmr_istop(S, sqrt(px), normb, maxiter, D.atol, D.btol, D.ctol);
       lsmr_recurrence(S, alpha, beta, damp, chb, cx, ch);
       if (istop) S[S_ITN] = itn0;
     }
@@ -1201,150 +1047,15 @@ __global__ void __launch_bounds__(TRF_THREADS) trf_nops_kernel(TrfDims D, TrfBuf
   }
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// Host: the 2-D trust-region subproblem (common.py solve_trust_region_2d).  np.roots of the quartic is
-// replaced by its real roots found by bracketing between the critical points (the roots of the derivative,
-// recursively) and bisecting; a root the polynomial only touches is not bracketed (numpy's companion
-// eigenvalues of such a root are a near-real complex pair, excluded there too unless exactly real).
-double poly_eval(const double* c, int d, double t) {
-  double v = c[0];
-  for (int i = 1; i <= d; ++i) v = v * t + c[i];
-  return v;
-}
-
-void poly_real_roots(const double* cin, int din, std::vector<double>& out) {
-  out.clear();
-  int s = 0;
-  while (s <= din && cin[s] == 0.0) ++s;  // leading zeros (np.roots strips them)
-  const int d = din - s;
-  if (d <= 0) return;
-  const double* c = cin + s;
-  if (d == 1) {
-    out.push_back(-c[1] / c[0]);
-    return;
-  }
-  if (d == 2) {
-    const double disc = c[1] * c[1] - 4 * c[0] * c[2];
-    if (disc < 0) return;
-    const double q = -0.5 * (c[1] + (c[1] >= 0 ? sqrt(disc) : -sqrt(disc)));
-    if (q != 0) {
-      out.push_back(q / c[0]);
-      out.push_back(c[2] / q);
-    } else {
-      out.push_back(0.0);
-      out.push_back(0.0);
-    }
-    std::sort(out.begin(), out.end());
-    return;
-  }
-  double dc[8];
-  for (int i = 0; i < d; ++i) dc[i] = c[i] * (d - i);
-  std::vector<double> crit;
-  poly_real_roots(dc, d - 1, crit);
-  double R = 0.0;
-  for (int i = 1; i <= d; ++i) R = std::max(R, std::fabs(c[i] / c[0]));
-  R += 1.0;
-  std::vector<double> pts;
-  pts.push_back(-R);
-  for (double x : crit)
-    if (x > -R && x < R) pts.push_back(x);
-  pts.push_back(R);
-  std::sort(pts.begin(), pts.end());
-  for (size_t i = 0; i + 1 < pts.size(); ++i) {
-    double a = pts[i], b = pts[i + 1];
-    double fa = poly_eval(c, d, a), fb = poly_eval(c, d, b);
-    if (fa == 0.0) {
-      if (out.empty() || out.back() != a) out.push_back(a);
-      continue;
-    }
-    if (fb == 0.0 || (fa < 0) == (fb < 0)) continue;
-    for (int it = 0; it < 200; ++it) {
-      const double m = 0.5 * (a + b);
-      if (m <= a || m >= b) break;
-      const double fm = poly_eval(c, d, m);
-      if (fm == 0.0) {
-        a = b = m;
-        break;
-      }
-      if ((fm < 0) == (fa < 0)) {
-        a = m;
-        fa = fm;
-      } else {
-        b = m;
-      }
-    }
-    out.push_back(0.5 * (a + b));
-  }
-  if (poly_eval(c, d, pts.back()) == 0.0) out.push_back(pts.back());
-}
-
-void solve_trust_region_2d(const double B[3], const double g[2], double Delta, double p[2]) {
-  // cho_factor (upper) + cho_solve, p = -B^-1 g, if B is positive definite and p lies inside
-  const double b00 = B[0], b01 = B[1], b11 = B[2];
-  if (b00 > 0) {
-    const double r00 = std::sqrt(b00), r01 = b01 / r00, s = b11 - r01 * r01;
-    if (s > 0) {
-      const double r11 = std::sqrt(s);
-      const double y0 = g[0] / r00, y1 = (g[1] - r01 * y0) / r11;  // R^T y = g
-      const double q1 = y1 / r11, q0 = (y0 - r01 * q1) / r00;      // R q = y
-      const double pn0 = -q0, pn1 = -q1;
-      if (pn0 * pn0 + pn1 * pn1 <= Delta * Delta) {
-        p[0] = pn0;
-        p[1] = pn1;
-        return;
-      }
-    }
-  }
-  const double a = b00 * Delta * Delta, b = b01 * Delta * Delta, c = b11 * Delta * Delta;
-  const double d = g[0] * Delta, f = g[1] * Delta;
-  const double co[5] = {-b + d, 2 * (a - c + f), 6 * b, 2 * (-a + c + f), -b - d};
-  std::vector<double> ts;
-  poly_real_roots(co, 4, ts);
-  if (ts.empty()) {
-    // No sign change (numpy's companion eigenvalues would all be complex here, and scipy's argmin over an empty
-    // set raises): the quartic's touching points -- critical points where it is zero to rounding -- are the
-    // boundary candidates; failing those, the Cauchy point -Delta g / |g|.
-    const double dco[4] = {4 * co[0], 3 * co[1], 2 * co[2], co[3]};
-    std::vector<double> crit;
-    poly_real_roots(dco, 3, crit);
-    double scale = 0.0;
-    for (double v : co) scale = std::max(scale, std::fabs(v));
-    for (double tt : crit) {
-      double mag = 0.0;  // |c_i t^(4-i)| summed: the rounding scale of the polynomial's value at t
-      for (int i = 0; i <= 4; ++i) mag += std::fabs(co[i]) * std::pow(std::fabs(tt), 4 - i);
-      if (std::fabs(poly_eval(co, 4, tt)) <= 64 * 2.220446049250313e-16 * (mag > 0 ? mag : scale)) ts.push_back(tt);
-    }
-    if (ts.empty()) {
-      const double gn = std::sqrt(g[0] * g[0] + g[1] * g[1]);
-      p[0] = gn > 0 ? -Delta * g[0] / gn : 0.0;
-      p[1] = gn > 0 ? -Delta * g[1] / gn : -Delta;
-      return;
-    }
-  }
-  double best = std::numeric_limits<double>::infinity();
-  p[0] = 0.0;
-  p[1] = -Delta;
-  bool any = false;
-  for (double tt : ts) {
-    const double q0 = Delta * (2 * tt / (1 + tt * tt)), q1 = Delta * ((1 - tt * tt) / (1 + tt * tt));
-    const double val = 0.5 * (q0 * (b00 * q0 + b01 * q1) + q1 * (b01 * q0 + b11 * q1)) + (g[0] * q0 + g[1] * q1);
-    if (!any || val < best) {
-      best = val;
-      p[0] = q0;
-      p[1] = q1;
-      any = true;
-    }
-  }
-}
-
 }  // namespace
 
 }  // namespace mq
 
 extern int mq_fail_host(const std::string& msg, int code);
 
-// The 2-D trust-region subproblem on the host (no HIP call): what optim_points' driver solves each trial step,
-// exposed so the CPU tests compare it with the numpy restatement (oracle/trf.py, scipy 1.15.3 common.py).
+// The 2-D trust-region subproblem on the host (no HIP call; trf_host.hpp): what both trf drivers solve each trial
+// step, exposed with argument checks so the CPU tests compare it with the numpy restatement (oracle/trf.py, scipy
+// 1.15.3 common.py).
 extern "C" int mq_trust_region_2d(const double* B, const double* g, double Delta, double* p) {
   if (!B || !g || !p) return mq_fail_host("mq_trust_region_2d: null argument", -1);
   if (!(Delta > 0) || !std::isfinite(Delta)) return mq_fail_host("mq_trust_region_2d: Delta must be finite and > 0", -2);
@@ -1379,7 +1090,7 @@ struct TrfDevCache {  // per host thread and device: capture stream, polling eve
   TrfBufs Bf{};
 };
 thread_local TrfDevCache g_trf_dev[TRF_MAX_DEV];
-}  // namespace  // lsmr iterations launched (one captured graph) between two reads of the done flags
+}  // namespace
 
 // dynamic LDS of the two per-iteration kernels for FB frames per block
 size_t trf_jt_lds(int FB, int n, int MR, int J, int C) {
@@ -1434,9 +1145,10 @@ size_t optim_trf_workspace_bytes(int B, int F, int J, int C, int NL) {
   return n * sizeof(double) + 256;
 }
 
-// Host driver (the trf_no_bounds loop).  x: device (B, NV) in/out.  stats[8 b + ...]: 0 initial cost, 1 final
-// cost, 2 iterations (njev - 1), 3 status (scipy's: 0 max_nfev, 1 gtol, 2 ftol, 3 xtol, 4 ftol and xtol),
-// 4 nfev, 5 njev, 6 lsmr iterations in total, 7 largest lsmr run.
+// Host driver: the trf_no_bounds loop (trf.py:401-540) as mq::TrfAnimal's steps with this solver's launches in
+// between.  x: device (B, NV) in/out.  stats[8 b + ...]: 0 initial cost, 1 final cost, 2 iterations (njev - 1),
+// 3 status (scipy's: 0 max_nfev, 1 gtol, 2 ftol, 3 xtol, 4 ftol and xtol), 4 nfev, 5 njev, 6 lsmr iterations in
+// total, 7 largest lsmr run.
 int optim_points_trf(const double* cams, int C, const double* p2d, double* x, int B, int F, int J, const int* cons_host,
                      int n_strong, int n_weak, const double* ssf_host, double scale_length, double scale_length_weak,
                      double rp, int loss, int n_deriv, int fix_lengths, int max_nfev_arg, double ftol, void* ws,
@@ -1670,7 +1382,7 @@ int optim_points_trf(const double* cams, int C, const double* p2d, double* x, in
   };
   // At a point p (x, or a trial point), for the animals in act: J, f, cost (mode 1), g = J^T f with its norms,
   // |p|, and J g (the next iteration's `regularize`).  Launched, then read after the next synchronisation.
-  std::vector<double> cost(B), gnorm2(B), ginf(B), rows(B), xnorm(B), areg(B);
+  std::vector<TrfAnimal> an(B);
   auto launch_jac = [&](double* p) {
     hipLaunchKernelGGL(trf_eval_kernel, grid, blk, 0, s, D, Bf, p, Bf.fres, 1);
     hipLaunchKernelGGL(trf_jt_kernel<0>, gridj, blk, jt_lds, s, D, Bf, 0);
@@ -1678,73 +1390,40 @@ int optim_points_trf(const double* cams, int C, const double* p2d, double* x, in
     hipLaunchKernelGGL(trf_jv_kernel, grid, blk, 0, s, D, Bf, (const double*)Bf.g, (const double*)nullptr);
   };
   auto read_jac = [&](int b) {
-    cost[b] = 0.5 * sum_field(hf, 4, 0, b);
-    rows[b] = sum_field(hf, 4, 2, b);
+    TrfAnimal& a = an[b];
+    a.cost = 0.5 * sum_field(hf, 4, 0, b);
+    a.rows = sum_field(hf, 4, 2, b);
     double gs = 0.0, m = 0.0;
     for (int k = 0; k < D.NBV; ++k) {
       gs += hg[((size_t)b * D.NBV + k) * 2];
       m = std::max(m, hg[((size_t)b * D.NBV + k) * 2 + 1]);
     }
-    gnorm2[b] = gs;
-    ginf[b] = m;
-    xnorm[b] = std::sqrt(sum_field(hn, TRF_NPF, 0, b));
-    areg[b] = 0.5 * sum_field(hj, 4, 0, b);
-  };
-  auto jac_and_grad = [&]() -> bool {
-    launch_jac(x);
-    if (!sync()) return false;
-    for (int b = 0; b < B; ++b) {
-      if (!act[b]) continue;
-      cost[b] = 0.5 * sum_field(hf, 4, 0, b);
-      rows[b] = sum_field(hf, 4, 2, b);
-      double gs = 0.0, m = 0.0;
-      for (int k = 0; k < D.NBV; ++k) {
-        gs += hg[((size_t)b * D.NBV + k) * 2];
-        m = std::max(m, hg[((size_t)b * D.NBV + k) * 2 + 1]);
-      }
-      gnorm2[b] = gs;
-      ginf[b] = m;
-      xnorm[b] = std::sqrt(sum_field(hn, TRF_NPF, 0, b));
-      areg[b] = 0.5 * sum_field(hj, 4, 0, b);
-    }
-    return true;
+    a.gnorm2 = gs;
+    a.ginf = m;
+    a.xnorm = std::sqrt(sum_field(hn, TRF_NPF, 0, b));
+    a.areg = 0.5 * sum_field(hj, 4, 0, b);
   };
 
   const int nparam = fix_lengths ? D.NX : D.NV;
-  const long long max_nfev = max_nfev_arg > 0 ? max_nfev_arg : 100LL * (fix_lengths ? D.NX : D.NV);
-  const double xtol = 1e-8, gtol = 1e-8;
-  enum { RUN, STOP };
-  std::vector<int> state(B, RUN), status(B, 0), lsmr_total(B, 0), lsmr_max(B, 0);
-  std::vector<long long> nfev(B, 1), njev(B, 1);
-  std::vector<double> Delta(B), damp(B), BS(3 * (size_t)B), gS(2 * (size_t)B), cost_new(B), actual(B);
-  if (!jac_and_grad()) return -3;
+  launch_jac(x);
+  if (!sync()) return -3;
   for (int b = 0; b < B; ++b) {
-    stats[8 * b + 0] = cost[b];
-    Delta[b] = xnorm[b] == 0 ? 1.0 : xnorm[b];
+    read_jac(b);
+    an[b].start(max_nfev_arg > 0 ? max_nfev_arg : 100LL * nparam);
+    stats[8 * b] = an[b].cost;  // (written here, so that a call that fails later leaves it too)
   }
   for (;;) {
     bool any = false;
-    for (int b = 0; b < B; ++b) {
-      act[b] = 0;
-      if (state[b] != RUN) continue;
-      if (ginf[b] < gtol) status[b] = 1;  // trf.py:463-465 (ftol stops end the loop below)
-      if (status[b] != 0 || nfev[b] == max_nfev) {
-        state[b] = STOP;
-        continue;
-      }
-      act[b] = 1;
-      any = true;
-    }
+    for (int b = 0; b < B; ++b) any |= (act[b] = an[b].begin_iteration());
     if (!any) break;
-    // regularize: the 1-D quadratic along -g inside the trust region (trf.py:480-484; J g from jac_and_grad)
+    double maxit = 0.0;
     for (int b = 0; b < B; ++b) {
       ctl[4 * b] = ctl[4 * b + 1] = ctl[4 * b + 2] = ctl[4 * b + 3] = 0.0;
       doneh[b] = act[b] ? 0 : 1;
       if (!act[b]) continue;
-      damp[b] = trf_regularize_damp(areg[b], gnorm2[b], Delta[b]);
-      ctl[4 * b] = damp[b];
-      ctl[4 * b + 1] = std::sqrt(2.0 * cost[b]);  // norm(f)
-      ctl[4 * b + 2] = std::min(rows[b], (double)nparam);
+      an[b].lsmr_setup(nparam, ctl[4 * b], ctl[4 * b + 2]);
+      ctl[4 * b + 1] = std::sqrt(2.0 * an[b].cost);  // norm(f)
+      maxit = std::max(maxit, ctl[4 * b + 2]);
     }
     if (!H2Drun(Bf.lctl, act_d + B,
                 {{Bf.lctl, ctl.data(), sizeof(double) * ctl.size()}, {done_d, doneh.data(), sizeof(int) * B},
@@ -1756,9 +1435,6 @@ int optim_points_trf(const double* cams, int C, const double* p2d, double* x, in
     hipLaunchKernelGGL(trf_lsmr1_kernel<true>, grid, blk, l1_lds, s, D, Bf, 1);
     hipLaunchKernelGGL(trf_jt_kernel<2>, gridj, blk, jt_lds, s, D, Bf, 1);
     int k = 2;  // the next iteration; every chunk starts at an even one
-    double maxit = 0.0;
-    for (int b = 0; b < B; ++b)
-      if (act[b]) maxit = std::max(maxit, ctl[4 * b + 2]);
     // chunks run back to back: the kernels write the done flags into host memory too, and the host reads them
     // once chunk i - 1 has finished, while chunk i runs (a finished animal's kernels return at once), so no
     // chunk waits on the host
@@ -1783,36 +1459,18 @@ int optim_points_trf(const double* cams, int C, const double* p2d, double* x, in
     if (!sync()) return -3;
     for (int b = 0; b < B; ++b) {
       if (!act[b]) continue;
-      const int it = (int)hitn[b];
-      lsmr_total[b] += it;
-      lsmr_max[b] = std::max(lsmr_max[b], it);
-      gS[2 * b] = sum_field(hn, TRF_NPF, 3, b);
-      gS[2 * b + 1] = sum_field(hn, TRF_NPF, 4, b);
-      BS[3 * b] = sum_field(hj, 4, 0, b);
-      BS[3 * b + 1] = sum_field(hj, 4, 2, b);
-      BS[3 * b + 2] = sum_field(hj, 4, 1, b);
+      TrfAnimal& a = an[b];
+      a.record_lsmr(hitn[b]);
+      a.g_S[0] = sum_field(hn, TRF_NPF, 3, b);
+      a.g_S[1] = sum_field(hn, TRF_NPF, 4, b);
+      a.B_S[0] = sum_field(hj, 4, 0, b);
+      a.B_S[1] = sum_field(hj, 4, 2, b);
+      a.B_S[2] = sum_field(hj, 4, 1, b);
     }
     // the trial steps (trf.py:496-540), every animal until it accepts, terminates or runs out of evaluations
-    std::vector<int> trial(B, 0);
-    for (int b = 0; b < B; ++b) {
-      trial[b] = act[b];
-      actual[b] = -1;
-    }
-    std::vector<double> pred(B), step_norm(B);
     for (;;) {
       bool anyt = false;
-      for (int b = 0; b < B; ++b) {
-        act[b] = trial[b] && actual[b] <= 0 && nfev[b] < max_nfev;
-        trial[b] = act[b];
-        if (!act[b]) continue;
-        anyt = true;
-        double p[2];
-        solve_trust_region_2d(&BS[3 * b], &gS[2 * b], Delta[b], p);
-        coef[4 * b] = p[0];
-        coef[4 * b + 1] = p[1];
-        const double q = p[0] * (BS[3 * b] * p[0] + BS[3 * b + 1] * p[1]) + p[1] * (BS[3 * b + 1] * p[0] + BS[3 * b + 2] * p[1]);
-        pred[b] = -(0.5 * q + (p[0] * gS[2 * b] + p[1] * gS[2 * b + 1]));
-      }
+      for (int b = 0; b < B; ++b) anyt |= (act[b] = an[b].propose_trial(&coef[4 * b]));
       if (!anyt) break;
       if (!H2Drun(act_d, Bf.coef + coef.size(),
                   {{act_d, act.data(), sizeof(int) * B}, {Bf.coef, coef.data(), sizeof(double) * coef.size()}}))
@@ -1823,37 +1481,15 @@ int optim_points_trf(const double* cams, int C, const double* p2d, double* x, in
       // rejected one loses nothing the next trial needs (that uses x, s1, s2 and the host's B_S, g_S).
       launch_jac(xt);
       if (!sync()) return -3;
-      for (int b = 0; b < B; ++b) {
-        if (!act[b]) continue;
-        nfev[b]++;
-        const double sh = std::sqrt(sum_field(hn, TRF_NPF, 5, b));
-        step_norm[b] = sh;
-        const double cn = 0.5 * sum_field(hf, 4, 0, b);
-        if (!std::isfinite(cn)) {
-          Delta[b] = 0.25 * sh;
-          actual[b] = -1;
-          continue;
-        }
-        cost_new[b] = cn;
-        actual[b] = cost[b] - cn;
-        double ratio;
-        const double Dn = trf_update_tr_radius(Delta[b], actual[b], pred[b], sh, sh > 0.95 * Delta[b], ratio);
-        const int term = trf_check_termination(actual[b], cost[b], sh, xnorm[b], ratio, ftol, xtol);
-        if (term) {
-          status[b] = term;
-          trial[b] = 0;
-          continue;
-        }
-        Delta[b] = Dn;
-      }
+      for (int b = 0; b < B; ++b)
+        if (act[b]) an[b].judge_trial(std::sqrt(sum_field(hn, TRF_NPF, 5, b)), 0.5 * sum_field(hf, 4, 0, b), ftol);
     }
     // accepted steps: x = x_new, with J, g, |x| and J g at x as the last trial evaluated them (trf.py:522-540)
     bool anya = false;
     for (int b = 0; b < B; ++b) {
-      act[b] = state[b] == RUN && actual[b] > 0;
+      act[b] = an[b].accept();
       if (!act[b]) continue;
       anya = true;
-      njev[b]++;
       read_jac(b);  // (the partials of the animal's last trial: it stopped trying at its accepted step)
     }
     if (anya) {
@@ -1875,15 +1511,7 @@ int optim_points_trf(const double* cams, int C, const double* p2d, double* x, in
 #endif
   if (!sync()) return -3;  // (the staging arena is the next call's)
   hs.dirty = false;
-  for (int b = 0; b < B; ++b) {
-    stats[8 * b + 1] = cost[b];
-    stats[8 * b + 2] = (double)(njev[b] - 1);
-    stats[8 * b + 3] = status[b];
-    stats[8 * b + 4] = (double)nfev[b];
-    stats[8 * b + 5] = (double)njev[b];
-    stats[8 * b + 6] = lsmr_total[b];
-    stats[8 * b + 7] = lsmr_max[b];
-  }
+  for (int b = 0; b < B; ++b) an[b].write_stats(stats + 8 * b);
   return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
