@@ -776,6 +776,57 @@ int mq_calibrate_views(mq_ctx* ctx, int model, int n_prob, const int* view_prefi
                        const double* obj, const double* img, const uint8_t* free_mask, double ftol, double xtol,
                        int max_iter, double* intrinsics, double* poses, double* resid, double* info, void* stream);
 
+/* ---- Chessboard corners (csrc/chessboard.hip, csrc/chessboard_dev.hpp): the detection the reference takes from
+ * OpenCV in analyze_chessboardvid (multicam_toolbox.py:22-72: cv2.findChessboardCorners :58, cv2.cornerSubPix :61),
+ * as a detector of this project's own for the 9 x 6 pattern.  tests/chessboard_ref.py is the numpy restatement:
+ * the response, the candidates and the grid are integer and equal it exactly; the refinement is float64 without FMA
+ * contraction.  OpenCV is not a dependency; parity with it is not pinned.  All pointers are device pointers; every
+ * call is stream-ordered with no host round trip (the context's workspace grows on the first call of a size).
+ * n_img in [0, 65535] (0 returns at once), height and width in [1, 32767].
+ *
+ * mq_chess_response (replaces the feature stage inside :58): gray uint8 (n_img, height, width) -> resp_out int32
+ * (n_img, height, width).  3 x 3 binomial blur ((1 2 1)^T (1 2 1), + 8 >> 4, replicated border), then ChESS
+ * (Bennett & Lasenby) on the ring of 16 samples at radius 5: R = max(0, 5 SR - 5 DR - |5 S - 16 L|), 0 in the
+ * 5-pixel border.
+ *
+ * mq_chess_candidates (:58): the pixels with R > 0 that equal the maximum of their 9 x 9 neighbourhood, the first
+ * max_candidates (in [1, 1024]) of them under (R descending, y ascending, x ascending): pos_out int32 (n_img,
+ * max_candidates, 2) [x, y], resp_out int32 (n_img, max_candidates), count_out int32 (n_img); rows past the count are
+ * zero.  A radix select over the unique keys (R << 32 | ~(y width + x)) and a sort: the same result on every call.
+ *
+ * mq_chess_grid (:58): per image, seeds in candidate order (at most 54) over the candidates with 4 R >= the
+ * strongest R; the nearest candidate and the nearest one more than 30 degrees off it span the first cell, and the
+ * grid grows by local prediction (2 p - p_opposite, or p + the neighbouring row's step) accepting the nearest unused
+ * candidate within 0.3 of the predicted step.  A seed is accepted with exactly 54 cells in a 9 x 6 block.  The order
+ * is objp's (:34-35): 9 along the fast axis, not mirrored (cross(c[1] - c[0], c[9] - c[0]) > 0, y down), and of the
+ * two orders 180 degrees apart the one whose first corner has the smaller (y, x).  found_out int32 (n_img);
+ * corners_out float64 (n_img, 54, 2) = p / scale + (1 / scale - 1) / 2, NaN when not found; index_out (null, or
+ * int32 (n_img, 54)) the candidate indices, -1 when not found.
+ *
+ * mq_corner_subpix (:61): cv2.cornerSubPix as documented -- window (2 win + 1)^2 with weights exp(-(i / win)^2)
+ * exp(-(j / win)^2), a (2 win + 3)^2 bilinear patch with replicated border per iteration, central differences, the
+ * 2 x 2 normal equations; stops on |det| <= eps_machine^2, a step <= eps, leaving the image, or max_iter iterations;
+ * a corner that moved more than win in x or y returns to its start.  corners float64 (n_img, per_image, 2) in / out
+ * (NaN stays NaN); found (null, or int32 (n_img)): the corners of an image with found == 0 are set to NaN.
+ * win in [1, 16].  One wave per corner.
+ *
+ * mq_find_chessboard (:57-61): frames uint8 BGR (height, width, 3), frame i at frames + i * frame_stride ->
+ * cvtColor(BGR2GRAY) -> detection on the copy reduced by scale (mq_cmc_preprocess's resize; scale = 1: the gray
+ * image itself) -> refinement on the full-size gray image.  max_candidates in [54, 1024].  Arguments out of range
+ * return -2 before anything is launched. */
+int mq_chess_response(mq_ctx* ctx, const uint8_t* gray, int n_img, int height, int width, int32_t* resp_out,
+                      void* stream);
+int mq_chess_candidates(mq_ctx* ctx, const int32_t* resp, int n_img, int height, int width, int max_candidates,
+                        int32_t* pos_out, int32_t* resp_out, int32_t* count_out, void* stream);
+int mq_chess_grid(mq_ctx* ctx, const int32_t* pos, const int32_t* resp, const int32_t* count, int n_img,
+                  int max_candidates, double scale, int32_t* found_out, double* corners_out, int32_t* index_out,
+                  void* stream);
+int mq_corner_subpix(mq_ctx* ctx, const uint8_t* gray, int n_img, int height, int width, double* corners,
+                     int per_image, const int32_t* found, int win, int max_iter, double eps, void* stream);
+int mq_find_chessboard(mq_ctx* ctx, const uint8_t* frames, int64_t frame_stride, int n_img, int height, int width,
+                       double scale, int win, int max_iter, double eps, int max_candidates, int32_t* found_out,
+                       double* corners_out, void* stream);
+
 /* ---- Motion-JPEG frames (csrc/jpeg.hip): a baseline JPEG encoder for the overlay frames, so that only the
  * compressed stream leaves the device.  tests/jpeg_ref.py is the numpy restatement, equal byte for byte: integer
  * arithmetic only, no atomics on global memory, the same bits on every call.

@@ -18,6 +18,8 @@
 #include "bundle.hpp"
 #include "calib.hpp"
 #include "candidates.hpp"
+#include "chessboard.hpp"
+#include "chessboard_dev.hpp"
 #include "cmc.hpp"
 #include "geometry.hpp"
 #include "overlay.hpp"
@@ -91,6 +93,7 @@ struct mq_ctx {
   DevBuf dlt_ws;    // mq_triangulate_dlt: undistorted points
   DevBuf ba_ws;     // mq_bundle_adjust: per-observation blocks, partials, trial points
   DevBuf calib_ws;  // mq_calib_init / mq_calibrate_views: problem description, per-view blocks, trial poses
+  DevBuf chess_ws;  // mq_chess_candidates / mq_find_chessboard: gray images, response, survivor map, select state, candidates
   DevBuf jpeg_ws;   // mq_jpeg_encode: coefficients, per-interval slots, lengths, offsets
   DevBuf jpeg_dec_ws;  // mq_jpeg_decode: coefficients, component planes, interval ends
   mq::SiftWs* sift_ws = nullptr;  // SIFT pyramid + candidates of the stage entry points (mq_sift_*)
@@ -251,6 +254,7 @@ int mq_destroy(mq_ctx* ctx) {
   ctx->dlt_ws.release();
   ctx->ba_ws.release();
   ctx->calib_ws.release();
+  ctx->chess_ws.release();
   ctx->jpeg_ws.release();
   ctx->jpeg_dec_ws.release();
   ctx->det_ws.release();
@@ -1994,6 +1998,115 @@ int mq_calibrate_views(mq_ctx* ctx, int model, int n_prob, const int* view_prefi
   const int rc = mq::calibrate_views(model, n_prob, V, N, view_prefix, pt_prefix, obj, img, free_mask, ftol, xtol,
                                      max_iter, intrinsics, poses, resid, info, ctx->calib_ws.p, (hipStream_t)stream);
   if (rc != 0) return fail("mq_calibrate_views: solver failed (" + std::to_string(rc) + ")", rc == -5 ? -5 : -6);
+  return 0;
+}
+
+/* ---- chessboard-corner detector (csrc/chessboard.hip) */
+namespace {
+
+size_t chess_align(size_t b) { return (b + 255) & ~(size_t)255; }
+
+int chess_dims_ok(int n, int h, int w) {
+  return n >= 0 && n <= 65535 && h >= 1 && w >= 1 && h <= 32767 && w <= 32767;
+}
+
+}  // namespace
+
+int mq_chess_response(mq_ctx* ctx, const uint8_t* gray, int n_img, int height, int width, int32_t* resp_out,
+                      void* stream) {
+  if (!ctx) return fail("mq_chess_response: null ctx");
+  if (!chess_dims_ok(n_img, height, width)) return fail("mq_chess_response: bad dims", -2);
+  if (n_img == 0) return 0;
+  if (!gray || !resp_out) return fail("mq_chess_response: null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  K_TRY(mq::chess_response(gray, n_img, height, width, resp_out, (hipStream_t)stream));
+  return 0;
+}
+
+int mq_chess_candidates(mq_ctx* ctx, const int32_t* resp, int n_img, int height, int width, int max_candidates,
+                        int32_t* pos_out, int32_t* resp_out, int32_t* count_out, void* stream) {
+  if (!ctx) return fail("mq_chess_candidates: null ctx");
+  if (!chess_dims_ok(n_img, height, width) || max_candidates < 1 || max_candidates > mq::CB_MAX_K)
+    return fail("mq_chess_candidates: bad dims (max_candidates in [1, 1024])", -2);
+  if (n_img == 0) return 0;
+  if (!resp || !pos_out || !resp_out || !count_out) return fail("mq_chess_candidates: null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (ctx->chess_ws.ensure(mq::chess_candidates_ws_bytes(n_img, height, width, max_candidates)))
+    return fail("mq_chess_candidates: out of device memory", -5);
+  K_TRY(mq::chess_candidates(resp, n_img, height, width, max_candidates, pos_out, resp_out, count_out,
+                             ctx->chess_ws.p, (hipStream_t)stream));
+  return 0;
+}
+
+int mq_chess_grid(mq_ctx* ctx, const int32_t* pos, const int32_t* resp, const int32_t* count, int n_img,
+                  int max_candidates, double scale, int32_t* found_out, double* corners_out, int32_t* index_out,
+                  void* stream) {
+  if (!ctx) return fail("mq_chess_grid: null ctx");
+  if (n_img < 0 || n_img > 65535 || max_candidates < 1 || max_candidates > mq::CB_MAX_K || !(scale > 0.0) || scale > 1.0)
+    return fail("mq_chess_grid: bad dims (max_candidates in [1, 1024], scale in (0, 1])", -2);
+  if (n_img == 0) return 0;
+  if (!pos || !resp || !count || !found_out || !corners_out) return fail("mq_chess_grid: null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  K_TRY(mq::chess_grid(pos, resp, count, n_img, max_candidates, scale, found_out, corners_out, index_out,
+                       (hipStream_t)stream));
+  return 0;
+}
+
+int mq_corner_subpix(mq_ctx* ctx, const uint8_t* gray, int n_img, int height, int width, double* corners,
+                     int per_image, const int32_t* found, int win, int max_iter, double eps, void* stream) {
+  if (!ctx) return fail("mq_corner_subpix: null ctx");
+  if (!chess_dims_ok(n_img, height, width) || per_image < 0 || per_image > 65535 || win < 1 || win > mq::CB_MAX_WIN ||
+      max_iter < 0 || !(eps >= 0.0))
+    return fail("mq_corner_subpix: bad dims (win in [1, 16], max_iter >= 0, eps >= 0)", -2);
+  if (n_img == 0 || per_image == 0) return 0;
+  if (!gray || !corners) return fail("mq_corner_subpix: null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  K_TRY(mq::corner_subpix(gray, n_img, height, width, corners, per_image, found, win, max_iter, eps,
+                          (hipStream_t)stream));
+  return 0;
+}
+
+int mq_find_chessboard(mq_ctx* ctx, const uint8_t* frames, int64_t frame_stride, int n_img, int height, int width,
+                       double scale, int win, int max_iter, double eps, int max_candidates, int32_t* found_out,
+                       double* corners_out, void* stream) {
+  if (!ctx) return fail("mq_find_chessboard: null ctx");
+  if (!chess_dims_ok(n_img, height, width) || height < 2 || width < 2 || !(scale > 0.0) || scale > 1.0 ||
+      max_candidates < mq::CB_NC || max_candidates > mq::CB_MAX_K || win < 1 || win > mq::CB_MAX_WIN || max_iter < 0 ||
+      !(eps >= 0.0) || frame_stride < (int64_t)height * width * 3)
+    return fail("mq_find_chessboard: bad dims (scale in (0, 1], max_candidates in [54, 1024], win in [1, 16])", -2);
+  if (n_img == 0) return 0;
+  if (!frames || !found_out || !corners_out) return fail("mq_find_chessboard: null argument");
+  const int h = scale == 1.0 ? height : (int)std::nearbyint(height * scale);
+  const int w = scale == 1.0 ? width : (int)std::nearbyint(width * scale);
+  if (h < 1 || w < 1) return fail("mq_find_chessboard: the reduced image is empty", -2);
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = (hipStream_t)stream;
+  const size_t n = (size_t)n_img, K = (size_t)max_candidates;
+  const size_t b_full = chess_align(n * height * width), b_small = scale == 1.0 ? 0 : chess_align(n * h * w);
+  const size_t b_resp = chess_align(n * h * w * 4), b_cand = mq::chess_candidates_ws_bytes(n_img, h, w, max_candidates);
+  const size_t b_pos = chess_align(n * K * 8), b_val = chess_align(n * K * 4), b_cnt = chess_align(n * 4);
+  if (ctx->chess_ws.ensure(b_cand + b_full + b_small + b_resp + b_pos + b_val + b_cnt))
+    return fail("mq_find_chessboard: out of device memory", -5);
+  char* p = ctx->chess_ws.as<char>();
+  void* cand_ws = p;  // first, where mq_chess_candidates keeps it
+  p += b_cand;
+  uint8_t* full = (uint8_t*)p;
+  p += b_full;
+  uint8_t* small = scale == 1.0 ? full : (uint8_t*)p;
+  p += b_small;
+  int32_t* resp = (int32_t*)p;
+  p += b_resp;
+  int32_t* pos = (int32_t*)p;
+  p += b_pos;
+  int32_t* val = (int32_t*)p;
+  p += b_val;
+  int32_t* cnt = (int32_t*)p;
+  K_TRY(mq::cmc_preprocess(frames, frame_stride, n_img, height, width, 1.0, full, s));
+  if (scale != 1.0) K_TRY(mq::cmc_preprocess(frames, frame_stride, n_img, height, width, scale, small, s));
+  K_TRY(mq::chess_response(small, n_img, h, w, resp, s));
+  K_TRY(mq::chess_candidates(resp, n_img, h, w, max_candidates, pos, val, cnt, cand_ws, s));
+  K_TRY(mq::chess_grid(pos, val, cnt, n_img, max_candidates, scale, found_out, corners_out, nullptr, s));
+  K_TRY(mq::corner_subpix(full, n_img, height, width, corners_out, mq::CB_NC, found_out, win, max_iter, eps, s));
   return 0;
 }
 

@@ -30,6 +30,7 @@ EXPORTED = [
     "mq_overlay_primitives", "mq_overlay_render",
     "mq_overlay_primitives_labelled", "mq_overlay_render_labelled", "mq_resize_bilinear",
     "mq_bundle_adjust", "mq_bundle_adjust_group", "mq_calib_init", "mq_calibrate_views",
+    "mq_chess_response", "mq_chess_candidates", "mq_chess_grid", "mq_corner_subpix", "mq_find_chessboard",
     "mq_jpeg_encode", "mq_jpeg_parse", "mq_jpeg_decode",
     "mq_decode_udp_topk", "mq_viterbi_filter_multi", "mq_triangulate_possible", "mq_optim_points_possible",
 ]
@@ -134,6 +135,11 @@ _SIGS = {
     "mq_bundle_adjust_group": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, vp, f64, f64, i32, vp, vp, vp]),
     "mq_calib_init": (i32, [vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
     "mq_calibrate_views": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, f64, f64, i32, vp, vp, vp, vp, vp]),
+    "mq_chess_response": (i32, [vp, vp, i32, i32, i32, vp, vp]),
+    "mq_chess_candidates": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "mq_chess_grid": (i32, [vp, vp, vp, vp, i32, i32, f64, vp, vp, vp, vp]),
+    "mq_corner_subpix": (i32, [vp, vp, i32, i32, i32, vp, i32, vp, i32, i32, f64, vp]),
+    "mq_find_chessboard": (i32, [vp, vp, i64, i32, i32, i32, f64, i32, i32, f64, i32, vp, vp, vp]),
     "mq_decode_udp_topk": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, f32, vp, vp, vp, vp, vp]),
     "mq_viterbi_filter_multi": (i32, [vp, vp, i32, i32, i32, i32, i32, f64, i32, f64, vp, vp]),
     "mq_triangulate_possible": (i32, [vp, vp, i32, vp, i32, i32, i32, f64, vp, vp, vp, vp, vp]),

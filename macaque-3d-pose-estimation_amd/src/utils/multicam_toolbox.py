@@ -7,12 +7,14 @@ dict path is supported (``camera_id``, ``K``, ``xi``, ``D`` and ``pmat`` = [R|t]
 per camera); the h5 path needs h5py, which this image lacks, and raises.
 Only omnidir undistortion is on the path (step2/3 call it with omnidir=True).
 
-The calibration chain from detected points onwards: ``calibrate_intrinsic`` (:74-116, chessboard corners ->
+The calibration chain: ``analyze_chessboardvid`` (:22-72, calibration video -> chessboard corners, detected in
+``mqhip.chessboard``, csrc/chessboard.hip; frame stores instead of mp4), ``calibrate_intrinsic`` (:74-116, chessboard corners ->
 ``cam_intrinsic.h5``'s ``mtx``, ``dist``, ``K``, ``xi``, ``D``) and ``get_extrinsic_from_cagekeypoints`` (:213-242,
 cage annotations -> ``cam_extrinsic.h5``'s ``rvec``, ``tvec``) fit cameras to points in ``mqhip.calib``
 (csrc/calib.hip); ``optimize_extrinsic`` / ``optimize_all_camera_params`` (:488-824) refine the rig on a marker
-trace in ``mqhip.bundle`` (csrc/bundle.hip) and produce the calibration the steps read.  What needs images stays
-out: chessboard / ArUco detection and the labelling GUI (:22-72, :118-211, :244-391).  ``fix_extrinsic_optim``
+trace in ``mqhip.bundle`` (csrc/bundle.hip) and produce the calibration the steps read.  What else needs images
+stays out: ArUco detection and the labelling GUI (:118-211, :244-391), ``saveimg`` (``cv2.drawChessboardCorners``)
+and mp4 input.  ``fix_extrinsic_optim``
 (:942-974) is not provided either: it edits ``cam_extrinsic_optim.h5`` in place through h5py's append mode and
 ``applytransform``, which is file surgery rather than array work.
 """
@@ -70,6 +72,87 @@ def _camera_ids(config_path):
     import yaml
     with open(config_path, 'r') as f:
         return yaml.safe_load(f)
+
+
+def chessboard_objp(square_size):
+    """:34-35: the board coordinates of the 54 inner corners, x fastest over 9, y over 6."""
+    objp = np.zeros((6 * 9, 3), np.float64)
+    objp[:, :2] = np.mgrid[0:9, 0:6].T.reshape(-1, 2) * square_size
+    return objp
+
+
+def analyze_chessboardvid(config_path, saveimg=False, frame_intv=5, *, stores=None, device: int = 0, batch: int = 8,
+                          win: int = 11, scale=None, square_size=None):
+    """multicam_toolbox.analyze_chessboardvid (:22-72) on the GPU.  Per camera id, frames ``range(10, n, frame_intv)``
+    (:50) of its calibration video go through ``mqhip.chessboard.find_chessboard_corners`` (BGR2GRAY, the 9 x 6
+    detector, ``cornerSubPix`` with window (win, win), zero zone (-1, -1), criteria (30, 0.001), :57-61) in batches
+    of ``batch``; the views where the board was found are kept.
+
+    ``stores`` = {camera id: frames}, uint8 (n, H, W, 3) BGR or (n, H, W) gray (a numpy array, an
+    ``mqhip.io.MjpegFrames`` or anything indexable by frame), keeps files out of it; ``square_size`` is then needed
+    unless ``config_path`` names a config with ``chessboard_square_size``.  Otherwise ``camera_id``,
+    ``chessboard_square_size`` and ``chessboard_vid_folder`` come from ``config_path`` and camera ``id`` reads the
+    frame store ``<chessboard_vid_folder>/<id>*`` (an ``mqhip.io.FrameStore`` directory, ``npy`` or ``mjpeg``; the
+    reference's ``<id>*.mp4`` is out of scope).
+
+    Returns {id: {'imp': (V, 54, 1, 2) float32, 'objp': (V, 54, 3) float64}}, what
+    ``calibrate_intrinsic(chessboard_points=...)`` takes, and writes ``chessboard_points.h5`` next to the config
+    (:40, :71-72) only when h5py imports and the frames came from the config's stores.  ``saveimg`` raises
+    ``NotImplementedError`` (``cv2.drawChessboardCorners``).  The default ``win`` is the reference's 11, which needs
+    corners more than about 24 px apart (mqhip.chessboard)."""
+    if saveimg:
+        raise NotImplementedError("saveimg draws with cv2.drawChessboardCorners, which this build does not have")
+    import glob
+
+    from mqhip import chessboard
+    from_cfg = stores is None
+    cfg = None
+    if from_cfg or square_size is None:
+        cfg = _camera_ids(config_path)
+        square_size = cfg['chessboard_square_size'] if square_size is None else square_size
+    if from_cfg:
+        from mqhip.io import FrameStore
+        vid_dir = os.path.dirname(config_path) + '/' + cfg['chessboard_vid_folder']
+        stores = {}
+        for i in cfg['camera_id']:
+            found = sorted(d for d in glob.glob(vid_dir + '/' + str(i) + '*') if os.path.isdir(d))
+            if not found:
+                raise FileNotFoundError(f"no frame store {vid_dir}/{i}* (mp4 input is out of scope)")
+            stores[i] = FrameStore(found[0], device=device)
+    objp = chessboard_objp(square_size)
+    out = {}
+    for i, frames in stores.items():
+        index = None
+        if hasattr(frames, 'frame_index'):          # a FrameStore: stored frame k is frames[frame_index[k]]
+            index, frames = frames.frame_index, frames.frames
+        n = len(frames) if index is None else len(index)
+        pick = list(range(10, n, frame_intv))
+        imgpoints = []
+        print(i)
+        for at in range(0, len(pick), max(1, int(batch))):
+            ks = pick[at:at + max(1, int(batch))]
+            ks = ks if index is None else [int(index[k]) for k in ks]
+            if hasattr(frames, 'device_frames'):
+                block = frames.device_frames(ks, device=device)
+            else:
+                block = np.stack([np.asarray(frames[k]) for k in ks])
+            ok, corners = chessboard.find_chessboard_corners(block, scale=scale, win=win, criteria=(30, 0.001),
+                                                             device=device)
+            imgpoints.extend(corners[v].astype(np.float32)[:, np.newaxis, :] for v in range(len(ks)) if ok[v])
+        V = len(imgpoints)
+        out[i] = {'imp': np.stack(imgpoints) if V else np.zeros((0, 54, 1, 2), np.float32),
+                  'objp': np.tile(objp[np.newaxis], (V, 1, 1))}
+    if from_cfg:
+        try:
+            import h5py
+        except ImportError:
+            h5py = None
+        if h5py is not None:
+            with h5py.File(os.path.dirname(config_path) + '/chessboard_points.h5', mode='w') as f:
+                for i, d in out.items():
+                    f.create_dataset('/' + str(i) + '/imp', data=d['imp'])
+                    f.create_dataset('/' + str(i) + '/objp', data=d['objp'])
+    return out
 
 
 def _h5_or_raise():
