@@ -827,6 +827,62 @@ int mq_find_chessboard(mq_ctx* ctx, const uint8_t* frames, int64_t frame_stride,
                        double scale, int win, int max_iter, double eps, int max_candidates, int32_t* found_out,
                        double* corners_out, void* stream);
 
+/* ---- ArUco markers (csrc/aruco.hip, csrc/aruco_dev.hpp): the detection the reference takes from OpenCV in
+ * analyze_aruco_marker_vid and analyze_aruco_cube_vid (multicam_toolbox.py:244-391: cv2.resize :281, :354,
+ * aruco.detectMarkers :283, :356), as a detector of this project's own for 4 x 4 codes in a one-cell border.  The
+ * caller passes the dictionary; cv2's predefined ones are not included.  tests/aruco_ref.py is the numpy restatement:
+ * the threshold, the labels and the components are integer and equal it exactly; the per-quad stage is float64 without
+ * FMA contraction.  OpenCV is not a dependency; parity with cv2.aruco is not pinned.  All pointers are device
+ * pointers; every call is stream-ordered with no host round trip (the context's workspace grows on the first call of a
+ * size).  n_img in [0, 65535] (0 returns at once), height and width in [1, 32767].  Arguments out of range return -2
+ * before anything is launched.
+ *
+ * mq_aruco_threshold (replaces the adaptive threshold inside :283): gray uint8 (n_img, height, width) -> dark_out
+ * uint8, 1 where gray * 529 < boxsum - 7 * 529 over the 23 x 23 window with replicated border.
+ *
+ * mq_aruco_label (the contour stage inside :283): dark -> labels_out int32 (n_img, height, width): the smallest
+ * linear index y * width + x of the pixel's 4-connected component of dark pixels, -1 where light.  A union-find with
+ * atomicMin in three launches; no thread waits on another.  The answer is unique.
+ *
+ * mq_aruco_components (:283): per component area, bounding box and the extreme pixel in the eight directions x, x+y,
+ * y, y-x, -x, -x-y, -y, x-y (the largest linear index among equal projections).  Candidates: area >= 100, both box
+ * sides >= 12, the box clear of the image border.  count_out int32 (n_img): their number; cand_out int32 (n_img,
+ * max_quads, 16): the first max_quads (in [1, 64]) in ascending label order: label, area, x0, y0, x1, y1, the eight
+ * extremes as linear indices, two zeros; rows past the count are zero.
+ *
+ * mq_aruco_quads (:283), one wave per candidate: the corners are the extremes of the diagonal or of the axis
+ * directions, whichever has the larger shoelace area (ties: diagonal); convex, sides >= 10 px, area / quad area in
+ * [1/16, 5/4].  Per side 16 bilinear profiles across it find where the gray level rises through its mid-level; a
+ * total-least-squares line per side; corners = intersections.  The square-to-quad homography samples 6 x 6 cells
+ * (3 x 3 samples each); the 20 border cells must be dark but for border_errors (in [0, 20]); the inner 16 are the
+ * code, row-major, white = 1.  dictionary: uint16 (n_codes in [1, 1024]) or null; the smallest Hamming distance over
+ * the four turns of every code (ties: lowest id, lowest turn), accepted up to max_correction_bits (in [0, 16]).
+ * ok_out / ids_out / rot_out int32 (n_img, max_quads); corners_out float64 (n_img, max_quads, 4, 2) in pixels of
+ * gray, corner 0 the marker's top-left, clockwise (cv2's order), NaN where not ok.  A null dictionary accepts every
+ * quad that passes the border test, with id -1 in the geometric order.
+ *
+ * mq_find_markers (:281-283, :354-356): frames uint8 BGR (height, width, 3), frame i at frames + i * frame_stride ->
+ * mq_resize_bilinear to (det_width, det_height) (in [2, frame size]) -> mq_cmc_preprocess at scale 1 (gray) -> the
+ * four stages -> count_out int32 (n_img), ids_out int32 (n_img, max_markers), corners_out float64 (n_img,
+ * max_markers, 4, 2) in frame pixels p * ratio + (ratio - 1) / 2 with ratio = frame size / detection size per axis
+ * (the reference's corner * rsize_ratio :289 without the half-pixel term), ordered by (id, label), NaN and -1 past
+ * the count.  max_markers in [1, max_quads].  cand_count_out (null, or int32 (n_img)): the candidates before
+ * max_quads cut them. */
+int mq_aruco_threshold(mq_ctx* ctx, const uint8_t* gray, int n_img, int height, int width, uint8_t* dark_out,
+                       void* stream);
+int mq_aruco_label(mq_ctx* ctx, const uint8_t* dark, int n_img, int height, int width, int32_t* labels_out,
+                   void* stream);
+int mq_aruco_components(mq_ctx* ctx, const int32_t* labels, int n_img, int height, int width, int max_quads,
+                        int32_t* count_out, int32_t* cand_out, void* stream);
+int mq_aruco_quads(mq_ctx* ctx, const uint8_t* gray, int n_img, int height, int width, const int32_t* count,
+                   const int32_t* cand, int max_quads, const uint16_t* dictionary, int n_codes,
+                   int max_correction_bits, int border_errors, int32_t* ok_out, int32_t* ids_out, int32_t* rot_out,
+                   double* corners_out, void* stream);
+int mq_find_markers(mq_ctx* ctx, const uint8_t* frames, int64_t frame_stride, int n_img, int height, int width,
+                    int det_width, int det_height, const uint16_t* dictionary, int n_codes, int max_correction_bits,
+                    int border_errors, int max_quads, int max_markers, int32_t* count_out, int32_t* ids_out,
+                    double* corners_out, int32_t* cand_count_out, void* stream);
+
 /* ---- Motion-JPEG frames (csrc/jpeg.hip): a baseline JPEG encoder for the overlay frames, so that only the
  * compressed stream leaves the device.  tests/jpeg_ref.py is the numpy restatement, equal byte for byte: integer
  * arithmetic only, no atomics on global memory, the same bits on every call.

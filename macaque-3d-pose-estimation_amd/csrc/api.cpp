@@ -17,6 +17,8 @@
 
 #include "bundle.hpp"
 #include "calib.hpp"
+#include "aruco.hpp"
+#include "aruco_dev.hpp"
 #include "candidates.hpp"
 #include "chessboard.hpp"
 #include "chessboard_dev.hpp"
@@ -94,6 +96,7 @@ struct mq_ctx {
   DevBuf ba_ws;     // mq_bundle_adjust: per-observation blocks, partials, trial points
   DevBuf calib_ws;  // mq_calib_init / mq_calibrate_views: problem description, per-view blocks, trial poses
   DevBuf chess_ws;  // mq_chess_candidates / mq_find_chessboard: gray images, response, survivor map, select state, candidates
+  DevBuf aruco_ws;  // mq_aruco_components / mq_find_markers: images, labels, areas, slots, candidates, per-quad results
   DevBuf jpeg_ws;   // mq_jpeg_encode: coefficients, per-interval slots, lengths, offsets
   DevBuf jpeg_dec_ws;  // mq_jpeg_decode: coefficients, component planes, interval ends
   mq::SiftWs* sift_ws = nullptr;  // SIFT pyramid + candidates of the stage entry points (mq_sift_*)
@@ -255,6 +258,7 @@ int mq_destroy(mq_ctx* ctx) {
   ctx->ba_ws.release();
   ctx->calib_ws.release();
   ctx->chess_ws.release();
+  ctx->aruco_ws.release();
   ctx->jpeg_ws.release();
   ctx->jpeg_dec_ws.release();
   ctx->det_ws.release();
@@ -2107,6 +2111,138 @@ int mq_find_chessboard(mq_ctx* ctx, const uint8_t* frames, int64_t frame_stride,
   K_TRY(mq::chess_candidates(resp, n_img, h, w, max_candidates, pos, val, cnt, cand_ws, s));
   K_TRY(mq::chess_grid(pos, val, cnt, n_img, max_candidates, scale, found_out, corners_out, nullptr, s));
   K_TRY(mq::corner_subpix(full, n_img, height, width, corners_out, mq::CB_NC, found_out, win, max_iter, eps, s));
+  return 0;
+}
+
+/* ---- ArUco-marker detector (csrc/aruco.hip) */
+namespace {
+
+int aruco_dims_ok(int n, int h, int w) {
+  return n >= 0 && n <= 65535 && h >= 1 && w >= 1 && h <= 32767 && w <= 32767;
+}
+
+}  // namespace
+
+int mq_aruco_threshold(mq_ctx* ctx, const uint8_t* gray, int n_img, int height, int width, uint8_t* dark_out,
+                       void* stream) {
+  if (!ctx) return fail("mq_aruco_threshold: null ctx");
+  if (!aruco_dims_ok(n_img, height, width)) return fail("mq_aruco_threshold: bad dims", -2);
+  if (n_img == 0) return 0;
+  if (!gray || !dark_out) return fail("mq_aruco_threshold: null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  K_TRY(mq::aruco_threshold(gray, n_img, height, width, dark_out, (hipStream_t)stream));
+  return 0;
+}
+
+int mq_aruco_label(mq_ctx* ctx, const uint8_t* dark, int n_img, int height, int width, int32_t* labels_out,
+                   void* stream) {
+  if (!ctx) return fail("mq_aruco_label: null ctx");
+  if (!aruco_dims_ok(n_img, height, width)) return fail("mq_aruco_label: bad dims", -2);
+  if (n_img == 0) return 0;
+  if (!dark || !labels_out) return fail("mq_aruco_label: null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  K_TRY(mq::aruco_label(dark, n_img, height, width, labels_out, (hipStream_t)stream));
+  return 0;
+}
+
+int mq_aruco_components(mq_ctx* ctx, const int32_t* labels, int n_img, int height, int width, int max_quads,
+                        int32_t* count_out, int32_t* cand_out, void* stream) {
+  if (!ctx) return fail("mq_aruco_components: null ctx");
+  if (!aruco_dims_ok(n_img, height, width) || max_quads < 1 || max_quads > mq::AR_MAX_QUADS)
+    return fail("mq_aruco_components: bad dims (max_quads in [1, 64])", -2);
+  if (n_img == 0) return 0;
+  if (!labels || !count_out || !cand_out) return fail("mq_aruco_components: null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (ctx->aruco_ws.ensure(mq::aruco_components_ws_bytes(n_img, height, width)))
+    return fail("mq_aruco_components: out of device memory", -5);
+  K_TRY(mq::aruco_components(labels, n_img, height, width, max_quads, count_out, cand_out, ctx->aruco_ws.p,
+                             (hipStream_t)stream));
+  return 0;
+}
+
+int mq_aruco_quads(mq_ctx* ctx, const uint8_t* gray, int n_img, int height, int width, const int32_t* count,
+                   const int32_t* cand, int max_quads, const uint16_t* dictionary, int n_codes,
+                   int max_correction_bits, int border_errors, int32_t* ok_out, int32_t* ids_out, int32_t* rot_out,
+                   double* corners_out, void* stream) {
+  if (!ctx) return fail("mq_aruco_quads: null ctx");
+  if (!aruco_dims_ok(n_img, height, width) || max_quads < 1 || max_quads > mq::AR_MAX_QUADS || n_codes < 0 ||
+      n_codes > mq::AR_MAX_CODES || (dictionary && n_codes < 1) || max_correction_bits < 0 ||
+      max_correction_bits > 16 || border_errors < 0 || border_errors > 20)
+    return fail("mq_aruco_quads: bad dims (max_quads in [1, 64], n_codes in [1, 1024], max_correction_bits in "
+                "[0, 16], border_errors in [0, 20])", -2);
+  if (n_img == 0) return 0;
+  if (!gray || !count || !cand || !ok_out || !ids_out || !rot_out || !corners_out)
+    return fail("mq_aruco_quads: null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  K_TRY(mq::aruco_quads(gray, n_img, height, width, count, cand, max_quads, dictionary, dictionary ? n_codes : 0,
+                        max_correction_bits, border_errors, ok_out, ids_out, rot_out, corners_out,
+                        (hipStream_t)stream));
+  return 0;
+}
+
+int mq_find_markers(mq_ctx* ctx, const uint8_t* frames, int64_t frame_stride, int n_img, int height, int width,
+                    int det_width, int det_height, const uint16_t* dictionary, int n_codes, int max_correction_bits,
+                    int border_errors, int max_quads, int max_markers, int32_t* count_out, int32_t* ids_out,
+                    double* corners_out, int32_t* cand_count_out, void* stream) {
+  if (!ctx) return fail("mq_find_markers: null ctx");
+  if (!aruco_dims_ok(n_img, height, width) || !aruco_dims_ok(n_img, det_height, det_width) || height < 2 ||
+      width < 2 || det_height < 2 || det_width < 2 || det_height > height || det_width > width || max_quads < 1 ||
+      max_quads > mq::AR_MAX_QUADS || max_markers < 1 || max_markers > max_quads || n_codes < 0 ||
+      n_codes > mq::AR_MAX_CODES || (dictionary && n_codes < 1) || max_correction_bits < 0 ||
+      max_correction_bits > 16 || border_errors < 0 || border_errors > 20 ||
+      frame_stride < (int64_t)height * width * 3)
+    return fail("mq_find_markers: bad dims (det size in [2, frame size], max_quads in [1, 64], max_markers in "
+                "[1, max_quads], n_codes in [1, 1024], max_correction_bits in [0, 16], border_errors in [0, 20])", -2);
+  if (n_img == 0) return 0;
+  if (!frames || !count_out || !ids_out || !corners_out) return fail("mq_find_markers: null argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = (hipStream_t)stream;
+  const bool resize = det_height != height || det_width != width;
+  const int h = det_height, w = det_width;
+  const size_t n = (size_t)n_img, Q = (size_t)max_quads;
+  const size_t b_comp = mq::aruco_components_ws_bytes(n_img, h, w);
+  const size_t b_small = resize ? chess_align(n * h * w * 3) : 0, b_gray = chess_align(n * h * w);
+  const size_t b_dark = chess_align(n * h * w), b_lab = chess_align(n * h * w * 4), b_cnt = chess_align(n * 4);
+  const size_t b_cand = chess_align(n * Q * mq::AR_CAND * 4), b_q = chess_align(n * Q * 4), b_c = chess_align(n * Q * 64);
+  if (ctx->aruco_ws.ensure(b_comp + b_small + b_gray + b_dark + b_lab + b_cnt + b_cand + 3 * b_q + b_c))
+    return fail("mq_find_markers: out of device memory", -5);
+  char* p = ctx->aruco_ws.as<char>();
+  void* comp_ws = p;  // first, where mq_aruco_components keeps it
+  p += b_comp;
+  uint8_t* small = (uint8_t*)p;
+  p += b_small;
+  uint8_t* gray = (uint8_t*)p;
+  p += b_gray;
+  uint8_t* dark = (uint8_t*)p;
+  p += b_dark;
+  int32_t* lab = (int32_t*)p;
+  p += b_lab;
+  int32_t* cnt = (int32_t*)p;
+  p += b_cnt;
+  int32_t* cand = (int32_t*)p;
+  p += b_cand;
+  int32_t* ok = (int32_t*)p;
+  p += b_q;
+  int32_t* ids = (int32_t*)p;
+  p += b_q;
+  int32_t* rot = (int32_t*)p;
+  p += b_q;
+  double* qc = (double*)p;
+  if (resize) {  // the reference's order (:281, :354): resize, then gray
+    K_TRY(mq::resize_bilinear(frames, frame_stride, n_img, height, width, small, (int64_t)h * w * 3, h, w, s));
+    K_TRY(mq::cmc_preprocess(small, (int64_t)h * w * 3, n_img, h, w, 1.0, gray, s));
+  } else {
+    K_TRY(mq::cmc_preprocess(frames, frame_stride, n_img, h, w, 1.0, gray, s));
+  }
+  K_TRY(mq::aruco_threshold(gray, n_img, h, w, dark, s));
+  K_TRY(mq::aruco_label(dark, n_img, h, w, lab, s));
+  K_TRY(mq::aruco_components(lab, n_img, h, w, max_quads, cnt, cand, comp_ws, s));
+  K_TRY(mq::aruco_quads(gray, n_img, h, w, cnt, cand, max_quads, dictionary, dictionary ? n_codes : 0,
+                        max_correction_bits, border_errors, ok, ids, rot, qc, s));
+  K_TRY(mq::aruco_collect(cnt, cand, ok, ids, qc, n_img, max_quads, max_markers, (double)width / (double)w,
+                          (double)height / (double)h, count_out, ids_out, corners_out, s));
+  if (cand_count_out)
+    HIP_TRY(hipMemcpyAsync(cand_count_out, cnt, n * 4, hipMemcpyDeviceToDevice, s));
   return 0;
 }
 

@@ -31,6 +31,7 @@ EXPORTED = [
     "mq_overlay_primitives_labelled", "mq_overlay_render_labelled", "mq_resize_bilinear",
     "mq_bundle_adjust", "mq_bundle_adjust_group", "mq_calib_init", "mq_calibrate_views",
     "mq_chess_response", "mq_chess_candidates", "mq_chess_grid", "mq_corner_subpix", "mq_find_chessboard",
+    "mq_aruco_threshold", "mq_aruco_label", "mq_aruco_components", "mq_aruco_quads", "mq_find_markers",
     "mq_jpeg_encode", "mq_jpeg_parse", "mq_jpeg_decode",
     "mq_decode_udp_topk", "mq_viterbi_filter_multi", "mq_triangulate_possible", "mq_optim_points_possible",
 ]
@@ -140,6 +141,11 @@ _SIGS = {
     "mq_chess_grid": (i32, [vp, vp, vp, vp, i32, i32, f64, vp, vp, vp, vp]),
     "mq_corner_subpix": (i32, [vp, vp, i32, i32, i32, vp, i32, vp, i32, i32, f64, vp]),
     "mq_find_chessboard": (i32, [vp, vp, i64, i32, i32, i32, f64, i32, i32, f64, i32, vp, vp, vp]),
+    "mq_aruco_threshold": (i32, [vp, vp, i32, i32, i32, vp, vp]),
+    "mq_aruco_label": (i32, [vp, vp, i32, i32, i32, vp, vp]),
+    "mq_aruco_components": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp]),
+    "mq_aruco_quads": (i32, [vp, vp, i32, i32, i32, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "mq_find_markers": (i32, [vp, vp, i64, i32, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
     "mq_decode_udp_topk": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, f32, vp, vp, vp, vp, vp]),
     "mq_viterbi_filter_multi": (i32, [vp, vp, i32, i32, i32, i32, i32, f64, i32, f64, vp, vp]),
     "mq_triangulate_possible": (i32, [vp, vp, i32, vp, i32, i32, i32, f64, vp, vp, vp, vp, vp]),

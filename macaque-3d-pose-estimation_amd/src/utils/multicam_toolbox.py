@@ -12,8 +12,11 @@ The calibration chain: ``analyze_chessboardvid`` (:22-72, calibration video -> c
 ``cam_intrinsic.h5``'s ``mtx``, ``dist``, ``K``, ``xi``, ``D``) and ``get_extrinsic_from_cagekeypoints`` (:213-242,
 cage annotations -> ``cam_extrinsic.h5``'s ``rvec``, ``tvec``) fit cameras to points in ``mqhip.calib``
 (csrc/calib.hip); ``optimize_extrinsic`` / ``optimize_all_camera_params`` (:488-824) refine the rig on a marker
-trace in ``mqhip.bundle`` (csrc/bundle.hip) and produce the calibration the steps read.  What else needs images
-stays out: ArUco detection and the labelling GUI (:118-211, :244-391), ``saveimg`` (``cv2.drawChessboardCorners``)
+trace in ``mqhip.bundle`` (csrc/bundle.hip) and produce the calibration the steps read.  That trace comes from
+``analyze_aruco_marker_vid`` / ``analyze_aruco_cube_vid`` (:244-391, marker video -> the marker's centre per frame,
+detected in ``mqhip.aruco``, csrc/aruco.hip; the caller passes the 4 x 4 dictionary), which live in the sibling
+module ``src.utils.multicam_aruco``: this module's own surface stays as it was.  What else needs images
+stays out: the labelling GUI (:118-211), ``saveimg`` (``cv2.drawChessboardCorners``), ``disp_result``
 and mp4 input.  ``fix_extrinsic_optim``
 (:942-974) is not provided either: it edits ``cam_extrinsic_optim.h5`` in place through h5py's append mode and
 ``applytransform``, which is file surgery rather than array work.
