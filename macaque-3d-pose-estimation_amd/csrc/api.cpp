@@ -31,6 +31,7 @@
 #include "detector.hpp"
 #include "idcls.hpp"
 #include "kernels.hpp"
+#include "workspace.hpp"
 #include "mq_hip.h"
 
 namespace {
@@ -54,10 +55,10 @@ int fail(const std::string& msg, int code = -1) {
     if (e_ != hipSuccess) return fail(std::string(#expr ": ") + hipGetErrorString(e_), -5); \
   } while (0)
 
-#define K_TRY(expr)                                              \
-  do {                                                           \
-    int r_ = (expr);                                             \
-    if (r_ != 0) return fail(std::string(#expr " failed"), -6);  \
+#define K_TRY(expr)                                                              \
+  do {                                                                           \
+    int r_ = (expr);                                                             \
+    if (r_ != 0) return fail(std::string(#expr " failed"), r_ == -5 ? -5 : -6);  \
   } while (0)
 
 struct DevBuf {
@@ -781,6 +782,24 @@ int mq_decode_udp_topk(mq_ctx* ctx, const float* heatmaps, int n, int J, int hm_
   return 0;
 }
 
+namespace {
+
+// mq_topdown's staging for n crops: the arrays follow each other unpadded
+struct TopdownBufs {
+  float *crops, *center, *scale, *hm;
+};
+
+TopdownBufs topdown_layout(mq::Carver& c, const mq_vitpose* m, int n) {
+  TopdownBufs b;
+  b.crops = c.take<float>((size_t)n * 3 * m->img_h * m->img_w, 4);
+  b.center = c.take<float>((size_t)n * 2, 4);
+  b.scale = c.take<float>((size_t)n * 2, 4);
+  b.hm = c.take<float>((size_t)n * m->J * 16 * m->T, 4);
+  return b;
+}
+
+}  // namespace
+
 int mq_topdown(mq_vitpose* m, const uint8_t* frames, int64_t frame_stride, int height, int width, const float* boxes,
                const int32_t* box_frame, int n, int flip_test, double* kp_img, float* score, int32_t* argmax,
                float* heatmaps, void* stream) {
@@ -789,20 +808,17 @@ int mq_topdown(mq_vitpose* m, const uint8_t* frames, int64_t frame_stride, int h
   HIP_TRY(hipSetDevice(m->ctx->device));
   // staging owned by the model (its device): crops, center/scale, heatmaps (if caller passes none).
   // Calls on one model are stream-ordered: the staging is reused by the next call on the model.
-  const size_t crop_b = (size_t)n * 3 * m->img_h * m->img_w * 4;
-  const size_t cs_b = (size_t)n * 4 * 4;
-  const size_t hm_b = (size_t)n * m->J * 16 * m->T * 4;
-  if (m->stage.ensure(crop_b + cs_b + hm_b + 1024)) return fail("mq_topdown: scratch alloc failed", -5);
-  char* b = m->stage.as<char>();
-  float* crops = (float*)b;
-  float* center = (float*)(b + crop_b);
-  float* scale = center + 2 * n;
-  float* hm = heatmaps ? heatmaps : (float*)(b + crop_b + cs_b);
-  int rc = mq_crop_udp(m->ctx, frames, frame_stride, height, width, boxes, box_frame, n, crops, center, scale, stream);
+  if (m->stage.ensure(mq::measure(topdown_layout, m, n))) return fail("mq_topdown: scratch alloc failed", -5);
+  mq::Carver c(m->stage.p, m->stage.bytes);
+  const TopdownBufs b = topdown_layout(c, m, n);
+  if (!c.fits()) return fail("mq_topdown: the staging does not hold its layout", -5);
+  float* hm = heatmaps ? heatmaps : b.hm;
+  int rc = mq_crop_udp(m->ctx, frames, frame_stride, height, width, boxes, box_frame, n, b.crops, b.center, b.scale,
+                       stream);
   if (rc) return rc;
-  rc = mq_vitpose_forward(m, crops, n, flip_test, hm, stream);
+  rc = mq_vitpose_forward(m, b.crops, n, flip_test, hm, stream);
   if (rc) return rc;
-  return mq_decode_udp(m->ctx, hm, n, m->J, 4 * m->gh, 4 * m->gw, center, scale, kp_img, score, argmax, nullptr,
+  return mq_decode_udp(m->ctx, hm, n, m->J, 4 * m->gh, 4 * m->gw, b.center, b.scale, kp_img, score, argmax, nullptr,
                        stream);
 }
 
@@ -1061,8 +1077,8 @@ int mq_nms(mq_ctx* ctx, const float* boxes, const float* scores, const uint8_t* 
   if (!boxes || !scores || !valid || !keep || !n_keep) return fail("mq_nms: null argument");
   if (n_img <= 0 || n_cand <= 0 || n_cand > 8192 || max_keep <= 0) return fail("mq_nms: 1 <= n_cand <= 8192", -2);
   if (ctx->det_ws.ensure(mq::nms_workspace_bytes(n_img, n_cand))) return fail("nms workspace alloc failed", -5);
-  K_TRY(mq::nms_batched(boxes, scores, valid, level, n_img, n_cand, iou_thr, max_keep, ctx->det_ws.p, keep, n_keep,
-                        (hipStream_t)stream));
+  K_TRY(mq::nms_batched(boxes, scores, valid, level, n_img, n_cand, iou_thr, max_keep, ctx->det_ws.p,
+                        ctx->det_ws.bytes, keep, n_keep, (hipStream_t)stream));
   return 0;
 }
 
@@ -1091,13 +1107,10 @@ int mq_rpn_proposals(mq_ctx* ctx, const float* head, int n_img, int n_levels, co
   }
   lv.cand_total = cand;
   if (cand > 8192) return fail("mq_rpn_proposals: more than 8192 candidates per image", -2);
-  int32_t* keep_buf = nullptr;
-  const size_t keep_bytes = ((size_t)n_img * max_keep * 4 + 255) & ~(size_t)255;
-  const size_t need = mq::rpn_workspace_bytes(n_img, rows, cand, n_levels) + keep_bytes;
-  if (ctx->det_ws.ensure(need)) return fail("rpn workspace alloc failed", -5);
-  keep_buf = reinterpret_cast<int32_t*>(ctx->det_ws.as<char>() + (need - keep_bytes));
-  K_TRY(mq::rpn_proposals(head, lv, n_img, rows, img_h, img_w, iou_thr, max_keep, ctx->det_ws.p, need - keep_bytes,
-                          proposals, scores, counts, keep_buf, (hipStream_t)stream));
+  if (ctx->det_ws.ensure(mq::rpn_workspace_bytes(n_img, rows, cand, max_keep)))
+    return fail("rpn workspace alloc failed", -5);
+  K_TRY(mq::rpn_proposals(head, lv, n_img, rows, img_h, img_w, iou_thr, max_keep, ctx->det_ws.p, ctx->det_ws.bytes,
+                          proposals, scores, counts, (hipStream_t)stream));
   return 0;
 }
 
@@ -1127,12 +1140,11 @@ int mq_rcnn_post(mq_ctx* ctx, const float* rois, const float* head, const int32_
   if (int rc = check_det(ctx)) return rc;
   if (!rois || !head || !counts || !det_boxes || !det_scores || !det_counts) return fail("mq_rcnn_post: null argument");
   if (n_img <= 0 || max_rois <= 0 || max_rois > 8192 || max_det <= 0) return fail("mq_rcnn_post: bad sizes", -2);
-  const size_t keep_bytes = ((size_t)n_img * max_det * 4 + 255) & ~(size_t)255;
-  const size_t need = mq::rcnn_workspace_bytes(n_img, max_rois) + keep_bytes;
-  if (ctx->det_ws.ensure(need)) return fail("rcnn workspace alloc failed", -5);
-  int32_t* keep_buf = reinterpret_cast<int32_t*>(ctx->det_ws.as<char>() + (need - keep_bytes));
+  if (ctx->det_ws.ensure(mq::rcnn_workspace_bytes(n_img, max_rois, max_det)))
+    return fail("rcnn workspace alloc failed", -5);
   K_TRY(mq::rcnn_post(rois, head, counts, n_img, max_rois, img_h, img_w, inv_scale_w, inv_scale_h, score_thr, iou_thr,
-                      max_det, ctx->det_ws.p, det_boxes, det_scores, det_counts, keep_buf, (hipStream_t)stream));
+                      max_det, ctx->det_ws.p, ctx->det_ws.bytes, det_boxes, det_scores, det_counts,
+                      (hipStream_t)stream));
   return 0;
 }
 
@@ -1248,11 +1260,9 @@ int mq_geometry_affinity(mq_ctx* ctx, const double* cams, int C, const double* p
   if ((int64_t)B * M == 0) return 0;
   if ((int64_t)B * M * M > (int64_t)1 << 31 || (int64_t)B * M * J > (int64_t)1 << 28)
     return fail("mq_geometry_affinity: batch too large", -2);
-  const size_t rays_b = ((size_t)B * M * J * 6 * 8 + 255) & ~(size_t)255;
-  if (ctx->assoc_ws.ensure(rays_b + (size_t)B * M * M * 8 + 256)) return fail("affinity workspace alloc failed", -5);
-  double* rays = ctx->assoc_ws.as<double>();
-  double* dist = reinterpret_cast<double*>(ctx->assoc_ws.as<char>() + rays_b);
-  K_TRY(mq::geometry_affinity(cams, C, points, cam_of_det, B, M, J, thr_kp, rays, dist, affinity, (hipStream_t)stream));
+  if (ctx->assoc_ws.ensure(mq::affinity_workspace_bytes(B, M, J))) return fail("affinity workspace alloc failed", -5);
+  K_TRY(mq::geometry_affinity(cams, C, points, cam_of_det, B, M, J, thr_kp, ctx->assoc_ws.p, ctx->assoc_ws.bytes,
+                              affinity, (hipStream_t)stream));
   return 0;
 }
 
@@ -1302,8 +1312,8 @@ int mq_match_svt(mq_ctx* ctx, const double* S, const int32_t* n_det, const int32
   if (!(mu > 0) || !(tol >= 0)) return fail("mq_match_svt: mu must be > 0 and tol >= 0", -2);
   HIP_TRY(hipSetDevice(ctx->device));
   if (ctx->assoc_ws.ensure(mq::match_svt_workspace_bytes(B, Nmax))) return fail("match_svt workspace alloc failed", -5);
-  K_TRY(mq::match_svt(S, n_det, cam_of_det, B, Nmax, alpha, lambda, mu, tol, max_iter, pselect, ctx->assoc_ws.p, match,
-                      x_out, iters, (hipStream_t)stream));
+  K_TRY(mq::match_svt(S, n_det, cam_of_det, B, Nmax, alpha, lambda, mu, tol, max_iter, pselect, ctx->assoc_ws.p,
+                      ctx->assoc_ws.bytes, match, x_out, iters, (hipStream_t)stream));
   return 0;
 }
 
@@ -1315,8 +1325,8 @@ int mq_viterbi_filter(mq_ctx* ctx, const double* kp, int A, int F, int C, int J,
   if ((int64_t)A * F * C * J == 0) return 0;
   HIP_TRY(hipSetDevice(ctx->device));
   if (ctx->scratch.ensure(mq::viterbi_scratch_bytes(A, F, C, J, n_back))) return fail("viterbi scratch alloc failed", -5);
-  K_TRY(mq::viterbi_filter(kp, A, F, C, J, score_threshold, n_back, offset_threshold, ctx->scratch.p, out,
-                           (hipStream_t)stream));
+  K_TRY(mq::viterbi_filter(kp, A, F, C, J, score_threshold, n_back, offset_threshold, ctx->scratch.p,
+                           ctx->scratch.bytes, out, (hipStream_t)stream));
   return 0;
 }
 
@@ -1331,8 +1341,8 @@ int mq_viterbi_filter_multi(mq_ctx* ctx, const double* kp, int A, int F, int C, 
   HIP_TRY(hipSetDevice(ctx->device));
   if (ctx->scratch.ensure(mq::viterbi_multi_scratch_bytes(A, F, C, J, K, n_back)))
     return fail("viterbi scratch alloc failed", -5);
-  K_TRY(mq::viterbi_filter_multi(kp, A, F, C, J, K, score_threshold, n_back, offset_threshold, ctx->scratch.p, out,
-                                 (hipStream_t)stream));
+  K_TRY(mq::viterbi_filter_multi(kp, A, F, C, J, K, score_threshold, n_back, offset_threshold, ctx->scratch.p,
+                                 ctx->scratch.bytes, out, (hipStream_t)stream));
   return 0;
 }
 
@@ -1358,23 +1368,24 @@ int mq_optim_points(mq_ctx* ctx, const double* cams, int C, const double* p2d, d
   const int NL = n_strong + n_weak;
   int rc;
   if (solver == 0) {
-    if (ctx->optim_ws.ensure(mq::optim_trf_workspace_bytes(B, F, J, C, NL)))
+    if (ctx->optim_ws.ensure(mq::optim_trf_workspace_bytes(B, F, J, C, NL, n_deriv_smooth)))
       return fail("optim workspace alloc failed", -5);
     rc = mq::optim_points_trf(cams, C, p2d, x, B, F, J, constraints, n_strong, n_weak, scale_smooth_full, scale_length,
                               scale_length_weak, reproj_error_threshold, reproj_loss, n_deriv_smooth, fix_lengths,
-                              max_iter, ftol, ctx->optim_ws.p, stats, (hipStream_t)stream);
+                              max_iter, ftol, ctx->optim_ws.p, ctx->optim_ws.bytes, stats, (hipStream_t)stream);
   } else {
     if (ctx->optim_ws.ensure(mq::optim_workspace_bytes(B, F, J, NL))) return fail("optim workspace alloc failed", -5);
     std::vector<double> st4(4 * (size_t)B, 0.0);
     rc = mq::optim_points(cams, C, p2d, x, B, F, J, constraints, n_strong, n_weak, scale_smooth_full, scale_length,
                           scale_length_weak, reproj_error_threshold, reproj_loss, n_deriv_smooth, fix_lengths,
-                          max_iter > 0 ? max_iter : 200, ftol, ctx->optim_ws.p, st4.data(), (hipStream_t)stream);
+                          max_iter > 0 ? max_iter : 200, ftol, ctx->optim_ws.p, ctx->optim_ws.bytes, st4.data(),
+                          (hipStream_t)stream);
     for (int b = 0; b < B; ++b) {
       for (int i = 0; i < 4; ++i) stats[8 * b + i] = st4[4 * b + i];
       for (int i = 4; i < 8; ++i) stats[8 * b + i] = 0.0;
     }
   }
-  if (rc != 0) return fail("mq_optim_points: solver failed (" + std::to_string(rc) + ")", -6);
+  if (rc != 0) return fail("mq_optim_points: solver failed (" + std::to_string(rc) + ")", rc == -5 ? -5 : -6);
   return 0;
 }
 
@@ -1402,13 +1413,13 @@ int mq_optim_points_possible(mq_ctx* ctx, const double* cams, int C, const doubl
   if (F <= n_deriv_smooth) return fail(std::string(me) + "needs more frames than n_deriv_smooth", -2);
   if ((int64_t)C * F * J * P > (int64_t)1 << 27) return fail(std::string(me) + "too many candidates per animal", -2);
   HIP_TRY(hipSetDevice(ctx->device));
-  if (ctx->optim_ws.ensure(mq::optim_possible_workspace_bytes(B, F, J, C, P, n_strong + n_weak)))
+  if (ctx->optim_ws.ensure(mq::optim_possible_workspace_bytes(B, F, J, C, P, n_strong + n_weak, n_deriv_smooth)))
     return fail("optim workspace alloc failed", -5);
   const int rc = mq::optim_points_possible(cams, C, p2d, x, alphas_norm, B, F, J, P, constraints, n_strong, n_weak,
                                            scale_smooth_full, scale_length, scale_length_weak, reproj_error_threshold,
-                                           reproj_loss, n_deriv_smooth, max_nfev, ftol, ctx->optim_ws.p, stats,
-                                           (hipStream_t)stream);
-  if (rc != 0) return fail(std::string(me) + "solver failed (" + std::to_string(rc) + ")", -6);
+                                           reproj_loss, n_deriv_smooth, max_nfev, ftol, ctx->optim_ws.p,
+                                           ctx->optim_ws.bytes, stats, (hipStream_t)stream);
+  if (rc != 0) return fail(std::string(me) + "solver failed (" + std::to_string(rc) + ")", rc == -5 ? -5 : -6);
   return 0;
 }
 
@@ -1445,8 +1456,6 @@ struct mq_cmc {
 
 namespace {
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 int cmc_reserve(mq_cmc* c, int n, int max_boxes) {
   if (n <= c->cap && max_boxes <= c->cap_boxes) return 0;
   n = std::max(n, c->cap);
@@ -1456,13 +1465,13 @@ int cmc_reserve(mq_cmc* c, int n, int max_boxes) {
                             N * K * 8, N * K * 8, N * 4,       N * 4,      N * 8,         N * 4,
                             N * 4,     N * K * 32, N * K * 32, N * 48,     N * (size_t)std::max(max_boxes, 1) * 32};
   size_t total = 0;
-  for (size_t b : sizes) total += align256(b);
+  for (size_t b : sizes) total += mq::align256(b);
   if (c->work.ensure(total)) return -1;
   char* p = c->work.as<char>();
   void* ptrs[17];
   for (int i = 0; i < 17; ++i) {
     ptrs[i] = p;
-    p += align256(sizes[i]);
+    p += mq::align256(sizes[i]);
   }
   c->gray = (uint8_t*)ptrs[0];
   c->mask = (uint8_t*)ptrs[1];
@@ -1841,7 +1850,7 @@ int mq_jpeg_encode(mq_ctx* ctx, const uint8_t* frames, int64_t frame_stride, int
   if (ctx->jpeg_ws.ensure(mq::jpeg_workspace_bytes(n, height, width, restart_interval)))
     return fail("mq_jpeg_encode: out of device memory", -5);
   K_TRY(mq::jpeg_encode(frames, frame_stride, n, height, width, restart_interval, hdr, q, out, out_stride, out_size,
-                        ctx->jpeg_ws.p, (hipStream_t)stream));
+                        ctx->jpeg_ws.p, ctx->jpeg_ws.bytes, (hipStream_t)stream));
   return 0;
 }
 
@@ -1862,7 +1871,7 @@ int mq_jpeg_decode(mq_ctx* ctx, const uint8_t* streams, int64_t stream_stride, c
   HIP_TRY(hipSetDevice(ctx->device));
   if (ctx->jpeg_dec_ws.ensure(need)) return fail("mq_jpeg_decode: out of device memory", -5);
   K_TRY(mq::jpeg_decode(streams, stream_stride, sizes, n, *info, g, frames, frame_stride, status, ctx->jpeg_dec_ws.p,
-                        (hipStream_t)stream));
+                        ctx->jpeg_dec_ws.bytes, (hipStream_t)stream));
   return 0;
 }
 
@@ -2008,10 +2017,30 @@ int mq_calibrate_views(mq_ctx* ctx, int model, int n_prob, const int* view_prefi
 /* ---- chessboard-corner detector (csrc/chessboard.hip) */
 namespace {
 
-size_t chess_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
-int chess_dims_ok(int n, int h, int w) {
+// the batch and image sizes the chessboard and the ArUco entry points take
+int image_dims_ok(int n, int h, int w) {
   return n >= 0 && n <= 65535 && h >= 1 && w >= 1 && h <= 32767 && w <= 32767;
+}
+
+// mq_find_chessboard's buffers: n images of height x width; detection on a copy reduced to h x w, or on `full`
+struct FindChessBufs {
+  mq::ChessCandBufs cand;
+  uint8_t *full, *small;
+  int32_t *resp, *pos, *val, *cnt;
+};
+
+FindChessBufs find_chess_layout(mq::Carver& c, int n_img, int height, int width, bool reduced, int h, int w, int K) {
+  const size_t n = (size_t)n_img;
+  FindChessBufs b;
+  b.cand = mq::chess_candidates_layout(c, n_img, h, w, K);
+  b.full = c.take<uint8_t>(n * height * width);
+  b.small = c.take<uint8_t>(reduced ? n * h * w : 0);
+  if (!reduced) b.small = b.full;
+  b.resp = c.take<int32_t>(n * h * w);
+  b.pos = c.take<int32_t>(n * K * 2);
+  b.val = c.take<int32_t>(n * K);
+  b.cnt = c.take<int32_t>(n);
+  return b;
 }
 
 }  // namespace
@@ -2019,7 +2048,7 @@ int chess_dims_ok(int n, int h, int w) {
 int mq_chess_response(mq_ctx* ctx, const uint8_t* gray, int n_img, int height, int width, int32_t* resp_out,
                       void* stream) {
   if (!ctx) return fail("mq_chess_response: null ctx");
-  if (!chess_dims_ok(n_img, height, width)) return fail("mq_chess_response: bad dims", -2);
+  if (!image_dims_ok(n_img, height, width)) return fail("mq_chess_response: bad dims", -2);
   if (n_img == 0) return 0;
   if (!gray || !resp_out) return fail("mq_chess_response: null argument");
   HIP_TRY(hipSetDevice(ctx->device));
@@ -2030,15 +2059,18 @@ int mq_chess_response(mq_ctx* ctx, const uint8_t* gray, int n_img, int height, i
 int mq_chess_candidates(mq_ctx* ctx, const int32_t* resp, int n_img, int height, int width, int max_candidates,
                         int32_t* pos_out, int32_t* resp_out, int32_t* count_out, void* stream) {
   if (!ctx) return fail("mq_chess_candidates: null ctx");
-  if (!chess_dims_ok(n_img, height, width) || max_candidates < 1 || max_candidates > mq::CB_MAX_K)
+  if (!image_dims_ok(n_img, height, width) || max_candidates < 1 || max_candidates > mq::CB_MAX_K)
     return fail("mq_chess_candidates: bad dims (max_candidates in [1, 1024])", -2);
   if (n_img == 0) return 0;
   if (!resp || !pos_out || !resp_out || !count_out) return fail("mq_chess_candidates: null argument");
   HIP_TRY(hipSetDevice(ctx->device));
   if (ctx->chess_ws.ensure(mq::chess_candidates_ws_bytes(n_img, height, width, max_candidates)))
     return fail("mq_chess_candidates: out of device memory", -5);
-  K_TRY(mq::chess_candidates(resp, n_img, height, width, max_candidates, pos_out, resp_out, count_out,
-                             ctx->chess_ws.p, (hipStream_t)stream));
+  mq::Carver c(ctx->chess_ws.p, ctx->chess_ws.bytes);
+  const mq::ChessCandBufs b = mq::chess_candidates_layout(c, n_img, height, width, max_candidates);
+  if (!c.fits()) return fail("mq_chess_candidates: the workspace does not hold its layout", -5);
+  K_TRY(mq::chess_candidates(resp, n_img, height, width, max_candidates, pos_out, resp_out, count_out, b,
+                             (hipStream_t)stream));
   return 0;
 }
 
@@ -2059,7 +2091,7 @@ int mq_chess_grid(mq_ctx* ctx, const int32_t* pos, const int32_t* resp, const in
 int mq_corner_subpix(mq_ctx* ctx, const uint8_t* gray, int n_img, int height, int width, double* corners,
                      int per_image, const int32_t* found, int win, int max_iter, double eps, void* stream) {
   if (!ctx) return fail("mq_corner_subpix: null ctx");
-  if (!chess_dims_ok(n_img, height, width) || per_image < 0 || per_image > 65535 || win < 1 || win > mq::CB_MAX_WIN ||
+  if (!image_dims_ok(n_img, height, width) || per_image < 0 || per_image > 65535 || win < 1 || win > mq::CB_MAX_WIN ||
       max_iter < 0 || !(eps >= 0.0))
     return fail("mq_corner_subpix: bad dims (win in [1, 16], max_iter >= 0, eps >= 0)", -2);
   if (n_img == 0 || per_image == 0) return 0;
@@ -2074,7 +2106,7 @@ int mq_find_chessboard(mq_ctx* ctx, const uint8_t* frames, int64_t frame_stride,
                        double scale, int win, int max_iter, double eps, int max_candidates, int32_t* found_out,
                        double* corners_out, void* stream) {
   if (!ctx) return fail("mq_find_chessboard: null ctx");
-  if (!chess_dims_ok(n_img, height, width) || height < 2 || width < 2 || !(scale > 0.0) || scale > 1.0 ||
+  if (!image_dims_ok(n_img, height, width) || height < 2 || width < 2 || !(scale > 0.0) || scale > 1.0 ||
       max_candidates < mq::CB_NC || max_candidates > mq::CB_MAX_K || win < 1 || win > mq::CB_MAX_WIN || max_iter < 0 ||
       !(eps >= 0.0) || frame_stride < (int64_t)height * width * 3)
     return fail("mq_find_chessboard: bad dims (scale in (0, 1], max_candidates in [54, 1024], win in [1, 16])", -2);
@@ -2085,40 +2117,46 @@ int mq_find_chessboard(mq_ctx* ctx, const uint8_t* frames, int64_t frame_stride,
   if (h < 1 || w < 1) return fail("mq_find_chessboard: the reduced image is empty", -2);
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = (hipStream_t)stream;
-  const size_t n = (size_t)n_img, K = (size_t)max_candidates;
-  const size_t b_full = chess_align(n * height * width), b_small = scale == 1.0 ? 0 : chess_align(n * h * w);
-  const size_t b_resp = chess_align(n * h * w * 4), b_cand = mq::chess_candidates_ws_bytes(n_img, h, w, max_candidates);
-  const size_t b_pos = chess_align(n * K * 8), b_val = chess_align(n * K * 4), b_cnt = chess_align(n * 4);
-  if (ctx->chess_ws.ensure(b_cand + b_full + b_small + b_resp + b_pos + b_val + b_cnt))
+  if (ctx->chess_ws.ensure(mq::measure(find_chess_layout, n_img, height, width, scale != 1.0, h, w, max_candidates)))
     return fail("mq_find_chessboard: out of device memory", -5);
-  char* p = ctx->chess_ws.as<char>();
-  void* cand_ws = p;  // first, where mq_chess_candidates keeps it
-  p += b_cand;
-  uint8_t* full = (uint8_t*)p;
-  p += b_full;
-  uint8_t* small = scale == 1.0 ? full : (uint8_t*)p;
-  p += b_small;
-  int32_t* resp = (int32_t*)p;
-  p += b_resp;
-  int32_t* pos = (int32_t*)p;
-  p += b_pos;
-  int32_t* val = (int32_t*)p;
-  p += b_val;
-  int32_t* cnt = (int32_t*)p;
-  K_TRY(mq::cmc_preprocess(frames, frame_stride, n_img, height, width, 1.0, full, s));
-  if (scale != 1.0) K_TRY(mq::cmc_preprocess(frames, frame_stride, n_img, height, width, scale, small, s));
-  K_TRY(mq::chess_response(small, n_img, h, w, resp, s));
-  K_TRY(mq::chess_candidates(resp, n_img, h, w, max_candidates, pos, val, cnt, cand_ws, s));
-  K_TRY(mq::chess_grid(pos, val, cnt, n_img, max_candidates, scale, found_out, corners_out, nullptr, s));
-  K_TRY(mq::corner_subpix(full, n_img, height, width, corners_out, mq::CB_NC, found_out, win, max_iter, eps, s));
+  mq::Carver c(ctx->chess_ws.p, ctx->chess_ws.bytes);
+  const FindChessBufs b = find_chess_layout(c, n_img, height, width, scale != 1.0, h, w, max_candidates);
+  if (!c.fits()) return fail("mq_find_chessboard: the workspace does not hold its layout", -5);
+  K_TRY(mq::cmc_preprocess(frames, frame_stride, n_img, height, width, 1.0, b.full, s));
+  if (scale != 1.0) K_TRY(mq::cmc_preprocess(frames, frame_stride, n_img, height, width, scale, b.small, s));
+  K_TRY(mq::chess_response(b.small, n_img, h, w, b.resp, s));
+  K_TRY(mq::chess_candidates(b.resp, n_img, h, w, max_candidates, b.pos, b.val, b.cnt, b.cand, s));
+  K_TRY(mq::chess_grid(b.pos, b.val, b.cnt, n_img, max_candidates, scale, found_out, corners_out, nullptr, s));
+  K_TRY(mq::corner_subpix(b.full, n_img, height, width, corners_out, mq::CB_NC, found_out, win, max_iter, eps, s));
   return 0;
 }
 
 /* ---- ArUco-marker detector (csrc/aruco.hip) */
 namespace {
 
-int aruco_dims_ok(int n, int h, int w) {
-  return n >= 0 && n <= 65535 && h >= 1 && w >= 1 && h <= 32767 && w <= 32767;
+// mq_find_markers' buffers: n images detected at h x w (from a resized BGR copy when the frames are larger), Q quads
+struct FindMarkersBufs {
+  mq::ArucoCompBufs comp;
+  uint8_t *small, *gray, *dark;
+  int32_t *lab, *cnt, *cand, *ok, *ids, *rot;
+  double* qc;
+};
+
+FindMarkersBufs find_markers_layout(mq::Carver& c, int n_img, int h, int w, bool resize, int max_quads) {
+  const size_t n = (size_t)n_img, Q = (size_t)max_quads;
+  FindMarkersBufs b;
+  b.comp = mq::aruco_components_layout(c, n_img, h, w);
+  b.small = c.take<uint8_t>(resize ? n * h * w * 3 : 0);
+  b.gray = c.take<uint8_t>(n * h * w);
+  b.dark = c.take<uint8_t>(n * h * w);
+  b.lab = c.take<int32_t>(n * h * w);
+  b.cnt = c.take<int32_t>(n);
+  b.cand = c.take<int32_t>(n * Q * mq::AR_CAND);
+  b.ok = c.take<int32_t>(n * Q);
+  b.ids = c.take<int32_t>(n * Q);
+  b.rot = c.take<int32_t>(n * Q);
+  b.qc = c.take<double>(n * Q * 8);
+  return b;
 }
 
 }  // namespace
@@ -2126,7 +2164,7 @@ int aruco_dims_ok(int n, int h, int w) {
 int mq_aruco_threshold(mq_ctx* ctx, const uint8_t* gray, int n_img, int height, int width, uint8_t* dark_out,
                        void* stream) {
   if (!ctx) return fail("mq_aruco_threshold: null ctx");
-  if (!aruco_dims_ok(n_img, height, width)) return fail("mq_aruco_threshold: bad dims", -2);
+  if (!image_dims_ok(n_img, height, width)) return fail("mq_aruco_threshold: bad dims", -2);
   if (n_img == 0) return 0;
   if (!gray || !dark_out) return fail("mq_aruco_threshold: null argument");
   HIP_TRY(hipSetDevice(ctx->device));
@@ -2137,7 +2175,7 @@ int mq_aruco_threshold(mq_ctx* ctx, const uint8_t* gray, int n_img, int height, 
 int mq_aruco_label(mq_ctx* ctx, const uint8_t* dark, int n_img, int height, int width, int32_t* labels_out,
                    void* stream) {
   if (!ctx) return fail("mq_aruco_label: null ctx");
-  if (!aruco_dims_ok(n_img, height, width)) return fail("mq_aruco_label: bad dims", -2);
+  if (!image_dims_ok(n_img, height, width)) return fail("mq_aruco_label: bad dims", -2);
   if (n_img == 0) return 0;
   if (!dark || !labels_out) return fail("mq_aruco_label: null argument");
   HIP_TRY(hipSetDevice(ctx->device));
@@ -2148,15 +2186,17 @@ int mq_aruco_label(mq_ctx* ctx, const uint8_t* dark, int n_img, int height, int 
 int mq_aruco_components(mq_ctx* ctx, const int32_t* labels, int n_img, int height, int width, int max_quads,
                         int32_t* count_out, int32_t* cand_out, void* stream) {
   if (!ctx) return fail("mq_aruco_components: null ctx");
-  if (!aruco_dims_ok(n_img, height, width) || max_quads < 1 || max_quads > mq::AR_MAX_QUADS)
+  if (!image_dims_ok(n_img, height, width) || max_quads < 1 || max_quads > mq::AR_MAX_QUADS)
     return fail("mq_aruco_components: bad dims (max_quads in [1, 64])", -2);
   if (n_img == 0) return 0;
   if (!labels || !count_out || !cand_out) return fail("mq_aruco_components: null argument");
   HIP_TRY(hipSetDevice(ctx->device));
   if (ctx->aruco_ws.ensure(mq::aruco_components_ws_bytes(n_img, height, width)))
     return fail("mq_aruco_components: out of device memory", -5);
-  K_TRY(mq::aruco_components(labels, n_img, height, width, max_quads, count_out, cand_out, ctx->aruco_ws.p,
-                             (hipStream_t)stream));
+  mq::Carver c(ctx->aruco_ws.p, ctx->aruco_ws.bytes);
+  const mq::ArucoCompBufs b = mq::aruco_components_layout(c, n_img, height, width);
+  if (!c.fits()) return fail("mq_aruco_components: the workspace does not hold its layout", -5);
+  K_TRY(mq::aruco_components(labels, n_img, height, width, max_quads, count_out, cand_out, b, (hipStream_t)stream));
   return 0;
 }
 
@@ -2165,7 +2205,7 @@ int mq_aruco_quads(mq_ctx* ctx, const uint8_t* gray, int n_img, int height, int 
                    int max_correction_bits, int border_errors, int32_t* ok_out, int32_t* ids_out, int32_t* rot_out,
                    double* corners_out, void* stream) {
   if (!ctx) return fail("mq_aruco_quads: null ctx");
-  if (!aruco_dims_ok(n_img, height, width) || max_quads < 1 || max_quads > mq::AR_MAX_QUADS || n_codes < 0 ||
+  if (!image_dims_ok(n_img, height, width) || max_quads < 1 || max_quads > mq::AR_MAX_QUADS || n_codes < 0 ||
       n_codes > mq::AR_MAX_CODES || (dictionary && n_codes < 1) || max_correction_bits < 0 ||
       max_correction_bits > 16 || border_errors < 0 || border_errors > 20)
     return fail("mq_aruco_quads: bad dims (max_quads in [1, 64], n_codes in [1, 1024], max_correction_bits in "
@@ -2185,7 +2225,7 @@ int mq_find_markers(mq_ctx* ctx, const uint8_t* frames, int64_t frame_stride, in
                     int border_errors, int max_quads, int max_markers, int32_t* count_out, int32_t* ids_out,
                     double* corners_out, int32_t* cand_count_out, void* stream) {
   if (!ctx) return fail("mq_find_markers: null ctx");
-  if (!aruco_dims_ok(n_img, height, width) || !aruco_dims_ok(n_img, det_height, det_width) || height < 2 ||
+  if (!image_dims_ok(n_img, height, width) || !image_dims_ok(n_img, det_height, det_width) || height < 2 ||
       width < 2 || det_height < 2 || det_width < 2 || det_height > height || det_width > width || max_quads < 1 ||
       max_quads > mq::AR_MAX_QUADS || max_markers < 1 || max_markers > max_quads || n_codes < 0 ||
       n_codes > mq::AR_MAX_CODES || (dictionary && n_codes < 1) || max_correction_bits < 0 ||
@@ -2199,50 +2239,26 @@ int mq_find_markers(mq_ctx* ctx, const uint8_t* frames, int64_t frame_stride, in
   hipStream_t s = (hipStream_t)stream;
   const bool resize = det_height != height || det_width != width;
   const int h = det_height, w = det_width;
-  const size_t n = (size_t)n_img, Q = (size_t)max_quads;
-  const size_t b_comp = mq::aruco_components_ws_bytes(n_img, h, w);
-  const size_t b_small = resize ? chess_align(n * h * w * 3) : 0, b_gray = chess_align(n * h * w);
-  const size_t b_dark = chess_align(n * h * w), b_lab = chess_align(n * h * w * 4), b_cnt = chess_align(n * 4);
-  const size_t b_cand = chess_align(n * Q * mq::AR_CAND * 4), b_q = chess_align(n * Q * 4), b_c = chess_align(n * Q * 64);
-  if (ctx->aruco_ws.ensure(b_comp + b_small + b_gray + b_dark + b_lab + b_cnt + b_cand + 3 * b_q + b_c))
+  if (ctx->aruco_ws.ensure(mq::measure(find_markers_layout, n_img, h, w, resize, max_quads)))
     return fail("mq_find_markers: out of device memory", -5);
-  char* p = ctx->aruco_ws.as<char>();
-  void* comp_ws = p;  // first, where mq_aruco_components keeps it
-  p += b_comp;
-  uint8_t* small = (uint8_t*)p;
-  p += b_small;
-  uint8_t* gray = (uint8_t*)p;
-  p += b_gray;
-  uint8_t* dark = (uint8_t*)p;
-  p += b_dark;
-  int32_t* lab = (int32_t*)p;
-  p += b_lab;
-  int32_t* cnt = (int32_t*)p;
-  p += b_cnt;
-  int32_t* cand = (int32_t*)p;
-  p += b_cand;
-  int32_t* ok = (int32_t*)p;
-  p += b_q;
-  int32_t* ids = (int32_t*)p;
-  p += b_q;
-  int32_t* rot = (int32_t*)p;
-  p += b_q;
-  double* qc = (double*)p;
+  mq::Carver c(ctx->aruco_ws.p, ctx->aruco_ws.bytes);
+  const FindMarkersBufs b = find_markers_layout(c, n_img, h, w, resize, max_quads);
+  if (!c.fits()) return fail("mq_find_markers: the workspace does not hold its layout", -5);
   if (resize) {  // the reference's order (:281, :354): resize, then gray
-    K_TRY(mq::resize_bilinear(frames, frame_stride, n_img, height, width, small, (int64_t)h * w * 3, h, w, s));
-    K_TRY(mq::cmc_preprocess(small, (int64_t)h * w * 3, n_img, h, w, 1.0, gray, s));
+    K_TRY(mq::resize_bilinear(frames, frame_stride, n_img, height, width, b.small, (int64_t)h * w * 3, h, w, s));
+    K_TRY(mq::cmc_preprocess(b.small, (int64_t)h * w * 3, n_img, h, w, 1.0, b.gray, s));
   } else {
-    K_TRY(mq::cmc_preprocess(frames, frame_stride, n_img, h, w, 1.0, gray, s));
+    K_TRY(mq::cmc_preprocess(frames, frame_stride, n_img, h, w, 1.0, b.gray, s));
   }
-  K_TRY(mq::aruco_threshold(gray, n_img, h, w, dark, s));
-  K_TRY(mq::aruco_label(dark, n_img, h, w, lab, s));
-  K_TRY(mq::aruco_components(lab, n_img, h, w, max_quads, cnt, cand, comp_ws, s));
-  K_TRY(mq::aruco_quads(gray, n_img, h, w, cnt, cand, max_quads, dictionary, dictionary ? n_codes : 0,
-                        max_correction_bits, border_errors, ok, ids, rot, qc, s));
-  K_TRY(mq::aruco_collect(cnt, cand, ok, ids, qc, n_img, max_quads, max_markers, (double)width / (double)w,
+  K_TRY(mq::aruco_threshold(b.gray, n_img, h, w, b.dark, s));
+  K_TRY(mq::aruco_label(b.dark, n_img, h, w, b.lab, s));
+  K_TRY(mq::aruco_components(b.lab, n_img, h, w, max_quads, b.cnt, b.cand, b.comp, s));
+  K_TRY(mq::aruco_quads(b.gray, n_img, h, w, b.cnt, b.cand, max_quads, dictionary, dictionary ? n_codes : 0,
+                        max_correction_bits, border_errors, b.ok, b.ids, b.rot, b.qc, s));
+  K_TRY(mq::aruco_collect(b.cnt, b.cand, b.ok, b.ids, b.qc, n_img, max_quads, max_markers, (double)width / (double)w,
                           (double)height / (double)h, count_out, ids_out, corners_out, s));
   if (cand_count_out)
-    HIP_TRY(hipMemcpyAsync(cand_count_out, cnt, n * 4, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(cand_count_out, b.cnt, (size_t)n_img * 4, hipMemcpyDeviceToDevice, s));
   return 0;
 }
 

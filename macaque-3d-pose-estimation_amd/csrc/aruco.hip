@@ -24,8 +24,6 @@ namespace {
 
 int launched() { return hipGetLastError() == hipSuccess ? 0 : -1; }
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // ------------------------------------------------------------------ 2. threshold
 constexpr int TT_W = 64, TT_H = 16;
 constexpr int TT_GW = TT_W + 2 * AR_THR_R, TT_GH = TT_H + 2 * AR_THR_R;
@@ -438,25 +436,27 @@ int aruco_label(const uint8_t* dark, int n, int h, int w, int32_t* labels, hipSt
   return launched();
 }
 
-size_t aruco_components_ws_bytes(int n, int h, int w) {
+ArucoCompBufs aruco_components_layout(Carver& c, int n, int h, int w) {
   const size_t nn = (size_t)(n > 0 ? n : 0);
-  return align256(nn * (size_t)h * (size_t)w * 4) + align256(nn * (size_t)max_slots_of(h, w) * sizeof(Slot)) +
-         align256(nn * 4);
+  ArucoCompBufs b;
+  b.n_area = nn * (size_t)h * (size_t)w;
+  b.area = c.take<int32_t>(b.n_area);
+  b.slots = c.take<Slot>(nn * (size_t)max_slots_of(h, w));
+  b.n_slots = c.take<int32_t>(nn);
+  return b;
 }
 
+size_t aruco_components_ws_bytes(int n, int h, int w) { return measure(aruco_components_layout, n, h, w); }
+
 int aruco_components(const int32_t* labels, int n, int h, int w, int max_quads, int32_t* count, int32_t* cand,
-                     void* ws, hipStream_t s) {
+                     const ArucoCompBufs& b, hipStream_t s) {
   if (n <= 0) return 0;
   if (max_quads < 1 || max_quads > AR_MAX_QUADS || (int64_t)h * w >= ((int64_t)1 << 31) || h > 65535) return -1;
   const int64_t hw = (int64_t)h * w;
   const int ms = max_slots_of(h, w);
-  char* base = (char*)ws;
-  int32_t* area = (int32_t*)base;
-  base += align256((size_t)n * hw * 4);
-  Slot* slots = (Slot*)base;
-  base += align256((size_t)n * ms * sizeof(Slot));
-  int32_t* n_slots = (int32_t*)base;
-  if (hipMemsetAsync(area, 0, (size_t)n * hw * 4, s) != hipSuccess) return -1;
+  int32_t *area = b.area, *n_slots = b.n_slots;
+  Slot* slots = static_cast<Slot*>(b.slots);
+  if (hipMemsetAsync(area, 0, b.n_area * sizeof(int32_t), s) != hipSuccess) return -1;
   hipLaunchKernelGGL(aruco_area_kernel, dim3((unsigned)((hw + 255) / 256), n), dim3(256), 0, s, labels, hw, area);
   hipLaunchKernelGGL(aruco_slots_kernel, dim3(n), dim3(1024), 0, s, labels, hw, area, slots, ms, n_slots);
   hipLaunchKernelGGL(aruco_stats_kernel, dim3((w + 255) / 256, h, n), dim3(256), 0, s, labels, h, w, area, slots, ms);

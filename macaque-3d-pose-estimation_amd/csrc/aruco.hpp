@@ -7,6 +7,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "workspace.hpp"
+
 namespace mq {
 
 // gray uint8 (n, h, w) -> dark uint8 (n, h, w): 1 where gray * 529 < boxsum - 7 * 529 over the 23 x 23 window
@@ -15,13 +17,20 @@ int aruco_threshold(const uint8_t* gray, int n, int h, int w, uint8_t* dark, hip
 // dark -> labels int32 (n, h, w): the smallest linear index of the pixel's 4-connected component, -1 where light
 int aruco_label(const uint8_t* dark, int n, int h, int w, int32_t* labels, hipStream_t s);
 
-// bytes of workspace aruco_components needs for n images of h x w
+// aruco_components' workspace for n images of h x w; a composite stage calls the layout on its own carver
+struct ArucoCompBufs {
+  int32_t* area;     // (n, h, w) pixel count at each component's label
+  void* slots;       // (n, max slots of h x w), aruco.hip's Slot
+  size_t n_area;
+  int32_t* n_slots;  // (n)
+};
+ArucoCompBufs aruco_components_layout(Carver& c, int n, int h, int w);
 size_t aruco_components_ws_bytes(int n, int h, int w);
 
 // labels -> count int32 (n): the components that pass the gates; cand int32 (n, max_quads, 16): the first max_quads
 // of them in ascending label order (label, area, x0, y0, x1, y1, 8 extreme pixels), rows past the count zero
 int aruco_components(const int32_t* labels, int n, int h, int w, int max_quads, int32_t* count, int32_t* cand,
-                     void* ws, hipStream_t s);
+                     const ArucoCompBufs& b, hipStream_t s);
 
 // candidates -> ok / ids / rot int32 (n, max_quads), corners float64 (n, max_quads, 4, 2) in pixels of gray (NaN
 // where not ok).  dict: uint16 (n_codes) or null.

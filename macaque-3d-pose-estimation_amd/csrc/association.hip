@@ -17,6 +17,7 @@
 // association workspace, L2-resident); A, E, T (Ne x (Ne+1), Ne = N rounded up to even) in LDS.
 #include "common.hpp"
 #include "geometry.hpp"
+#include "workspace.hpp"
 
 namespace mq {
 namespace {
@@ -286,15 +287,21 @@ __global__ __launch_bounds__(SVT_THREADS) void match_svt_kernel(
   if (tid == 0) iters[b] = it < max_iter ? it : max_iter - 1;
 }
 
+// three Nmax x Nmax matrices per keyframe
+double* match_svt_layout(Carver& c, int B, int Nmax) { return c.take<double>((size_t)B * 3 * Nmax * Nmax); }
+
 }  // namespace
 
-size_t match_svt_workspace_bytes(int B, int Nmax) { return (size_t)B * 3 * Nmax * Nmax * sizeof(double) + 256; }
+size_t match_svt_workspace_bytes(int B, int Nmax) { return measure(match_svt_layout, B, Nmax); }
 
 int match_svt(const double* S, const int32_t* n_det, const int32_t* cam_of_det, int B, int Nmax, double alpha,
-              double lambda, double mu, double tol, int max_iter, int pselect, void* ws, uint8_t* match,
-              double* x_out, int32_t* iters, hipStream_t s) {
+              double lambda, double mu, double tol, int max_iter, int pselect, void* ws, size_t ws_bytes,
+              uint8_t* match, double* x_out, int32_t* iters, hipStream_t s) {
   if (B <= 0) return 0;
   if (Nmax < 1 || Nmax > SVT_MAX_N) return -2;
+  Carver c(ws, ws_bytes);
+  double* mats = match_svt_layout(c, B, Nmax);
+  if (!c.fits()) return -5;
   const int Ne = Nmax + (Nmax & 1);
   const size_t lds = (size_t)3 * Ne * (Ne + 1) * sizeof(double);
   static size_t attr_lds = 0;  // dynamic LDS above the 64 KB default needs the attribute (static LDS counts too)
@@ -305,7 +312,7 @@ int match_svt(const double* S, const int32_t* n_det, const int32_t* cam_of_det, 
     attr_lds = lds;
   }
   hipLaunchKernelGGL(match_svt_kernel, dim3(B), dim3(SVT_THREADS), lds, s, S, n_det, cam_of_det, Nmax, alpha, lambda,
-                     mu, tol, max_iter, pselect, static_cast<double*>(ws), match, x_out, iters);
+                     mu, tol, max_iter, pselect, mats, match, x_out, iters);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -9,6 +9,7 @@
 #include "candidates.hpp"
 #include "dlt_dev.hpp"
 #include "viterbi_dev.hpp"
+#include "workspace.hpp"
 
 namespace mq {
 
@@ -183,19 +184,29 @@ __global__ __launch_bounds__(VM_LANES) void viterbi_multi_kernel(VitMulti V, int
   }
 }
 
-size_t viterbi_multi_scratch_bytes(int A, int F, int C, int J, int K, int n_back) {
-  return (size_t)A * C * J * F * K * n_back + 512;
+namespace {
+
+// the back-pointers [chain][F][K * n_back]; a frame's slot 0 holds the path once it is walked
+int8_t* viterbi_multi_layout(Carver& c, int A, int F, int C, int J, int K, int n_back) {
+  return c.take<int8_t>((size_t)A * C * J * F * K * n_back);
 }
 
-// scratch: viterbi_multi_scratch_bytes() -- back-pointers, then the path.
+}  // namespace
+
+size_t viterbi_multi_scratch_bytes(int A, int F, int C, int J, int K, int n_back) {
+  return measure(viterbi_multi_layout, A, F, C, J, K, n_back);
+}
+
 int viterbi_filter_multi(const double* kp, int A, int F, int C, int J, int K, double score_thr, int n_back,
-                         double thres_dist, void* scratch, double* out, hipStream_t s) {
+                         double thres_dist, void* scratch, size_t scratch_bytes, double* out, hipStream_t s) {
   const int chains = A * C * J;
   if (chains <= 0 || F <= 0) return 0;
   if (n_back > 3 || n_back < 1 || K < 1 || K > CAND_MAX) return -2;
+  Carver c(scratch, scratch_bytes);
+  int8_t* bk = viterbi_multi_layout(c, A, F, C, J, K, n_back);
+  if (!c.fits()) return -5;
   VitMulti V{kp, F, C, J, K, n_back, score_thr};
-  hipLaunchKernelGGL(viterbi_multi_kernel, dim3(chains), dim3(VM_LANES), 0, s, V, chains, thres_dist,
-                     static_cast<int8_t*>(scratch), out);
+  hipLaunchKernelGGL(viterbi_multi_kernel, dim3(chains), dim3(VM_LANES), 0, s, V, chains, thres_dist, bk, out);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

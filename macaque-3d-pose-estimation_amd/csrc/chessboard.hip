@@ -254,8 +254,6 @@ int next_pow2(int v) {
   return p;
 }
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // ------------------------------------------------------------------ 4-5. grid
 __global__ __launch_bounds__(CB_LANES) void chess_grid_kernel(const int32_t* __restrict__ pos,
                                                               const int32_t* __restrict__ val,
@@ -331,11 +329,17 @@ __global__ __launch_bounds__(CB_LANES) void corner_subpix_kernel(const uint8_t* 
 
 }  // namespace
 
-size_t chess_candidates_ws_bytes(int n, int h, int w, int K) {
+ChessCandBufs chess_candidates_layout(Carver& c, int n, int h, int w, int K) {
   const size_t nn = (size_t)(n > 0 ? n : 0);
-  return align256(nn * (size_t)h * (size_t)w * 4) + align256(nn * 256 * 4) + align256(nn * sizeof(SelState)) +
-         align256(nn * (size_t)next_pow2(K) * 8);
+  ChessCandBufs b;
+  b.surv = c.take<int32_t>(nn * (size_t)h * (size_t)w);
+  b.hist = c.take<uint32_t>(nn * 256);
+  b.st = c.take<SelState>(nn);
+  b.keys = c.take<unsigned long long>(nn * (size_t)next_pow2(K));
+  return b;
 }
+
+size_t chess_candidates_ws_bytes(int n, int h, int w, int K) { return measure(chess_candidates_layout, n, h, w, K); }
 
 int chess_response(const uint8_t* gray, int n, int h, int w, int32_t* resp, hipStream_t s) {
   if (n <= 0) return 0;
@@ -345,19 +349,15 @@ int chess_response(const uint8_t* gray, int n, int h, int w, int32_t* resp, hipS
 }
 
 int chess_candidates(const int32_t* resp, int n, int h, int w, int K, int32_t* pos, int32_t* val, int32_t* count,
-                     void* ws, hipStream_t s) {
+                     const ChessCandBufs& b, hipStream_t s) {
   if (n <= 0) return 0;
   if (K < 1 || K > CB_MAX_K || (int64_t)h * w >= ((int64_t)1 << 31)) return -1;
   const int64_t hw = (int64_t)h * w;
   const int kpad = next_pow2(K);
-  char* base = (char*)ws;
-  int32_t* surv = (int32_t*)base;
-  base += align256((size_t)n * hw * 4);
-  uint32_t* hist = (uint32_t*)base;
-  base += align256((size_t)n * 256 * 4);
-  SelState* st = (SelState*)base;
-  base += align256((size_t)n * sizeof(SelState));
-  unsigned long long* keys = (unsigned long long*)base;
+  int32_t* surv = b.surv;
+  uint32_t* hist = b.hist;
+  SelState* st = static_cast<SelState*>(b.st);
+  unsigned long long* keys = b.keys;
   hipLaunchKernelGGL(chess_nms_kernel, dim3((w + NT_W - 1) / NT_W, (h + NT_H - 1) / NT_H, n), dim3(256), 0, s, resp,
                      h, w, surv);
   hipLaunchKernelGGL(chess_sel_init_kernel, dim3(n), dim3(256), 0, s, st, hist, n, K);

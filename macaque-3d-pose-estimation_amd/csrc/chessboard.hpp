@@ -7,9 +7,18 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "workspace.hpp"
+
 namespace mq {
 
-// bytes of workspace chess_candidates needs for n images of h x w (survivor map, histograms, select state, keys)
+// chess_candidates' workspace for n images of h x w; a composite stage calls the layout on its own carver
+struct ChessCandBufs {
+  int32_t* surv;             // survivor map (n, h, w)
+  uint32_t* hist;            // (n, 256)
+  void* st;                  // select state (n), chessboard.hip's SelState
+  unsigned long long* keys;  // (n, next power of two >= K)
+};
+ChessCandBufs chess_candidates_layout(Carver& c, int n, int h, int w, int K);
 size_t chess_candidates_ws_bytes(int n, int h, int w, int K);
 
 // gray uint8 (n, h, w) -> resp int32 (n, h, w): ChESS on the 3 x 3 binomial blur, 0 in the 5-pixel border
@@ -18,7 +27,7 @@ int chess_response(const uint8_t* gray, int n, int h, int w, int32_t* resp, hipS
 // resp -> pos int32 (n, K, 2) [x, y], val int32 (n, K), count int32 (n): the 9 x 9 maxima with R > 0, the first K
 // under (R descending, y ascending, x ascending); rows past count are zero.  1 <= K <= 1024; h * w < 2^31.
 int chess_candidates(const int32_t* resp, int n, int h, int w, int K, int32_t* pos, int32_t* val, int32_t* count,
-                     void* ws, hipStream_t s);
+                     const ChessCandBufs& b, hipStream_t s);
 
 // candidates -> found int32 (n), corners float64 (n, 54, 2) in full-frame pixels (NaN when not found), idx int32
 // (n, 54) candidate indices (-1 when not found; may be null)

@@ -25,6 +25,7 @@
 
 #include "common.hpp"
 #include "detector.hpp"
+#include "workspace.hpp"
 
 namespace mq {
 namespace {
@@ -797,82 +798,136 @@ int subsample2(const float* x, int n_img, int H, int W, int C, float* out, hipSt
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-size_t nms_workspace_bytes(int n_img, int n_cand) {
-  const int words = (n_cand + 63) / 64;
-  return (size_t)n_img * n_cand * (4 + 16) + (size_t)n_img * n_cand * words * 8 + (size_t)n_img * 4 + 1024;
+namespace {
+
+// order and sboxes follow each other unpadded from the block's 256-byte start; mask is at 256
+struct NmsBufs {
+  int32_t* order;
+  float* sboxes;
+  unsigned long long* mask;
+  int32_t* nv;
+};
+
+NmsBufs nms_layout(Carver& c, int n_img, int n_cand) {
+  const size_t nc = (size_t)n_img * n_cand, words = (n_cand + 63) / 64;
+  NmsBufs b;
+  b.order = c.take<int32_t>(nc);
+  b.sboxes = c.take<float>(nc * 4, 4);
+  b.mask = c.take<unsigned long long>(nc * words);
+  b.nv = c.take<int32_t>(n_img, 4);
+  return b;
 }
 
-int nms_batched(const float* boxes, const float* scores, const uint8_t* valid, const int8_t* lvl, int n_img,
-                int n_cand, float thr, int max_keep, void* ws, int32_t* keep, int32_t* n_keep, hipStream_t s) {
-  if (n_cand > NMS_SORT_MAX) return -2;
+int nms_launch(const float* boxes, const float* scores, const uint8_t* valid, const int8_t* lvl, int n_img, int n_cand,
+               float thr, int max_keep, const NmsBufs& b, int32_t* keep, int32_t* n_keep, hipStream_t s) {
   const int words = (n_cand + 63) / 64;
-  if (words > 128) return -2;
-  char* p = static_cast<char*>(ws);
-  int32_t* order = reinterpret_cast<int32_t*>(p);
-  p += (size_t)n_img * n_cand * 4;
-  float* sboxes = reinterpret_cast<float*>(p);
-  p += (size_t)n_img * n_cand * 16;
-  unsigned long long* mask = reinterpret_cast<unsigned long long*>(((uintptr_t)p + 255) & ~(uintptr_t)255);
-  p = reinterpret_cast<char*>(mask) + (size_t)n_img * n_cand * words * 8;
-  int32_t* nv = reinterpret_cast<int32_t*>(p);
-  hipLaunchKernelGGL(nms_sort_kernel, dim3(n_img), dim3(NMS_T), 0, s, boxes, scores, valid, lvl, n_cand, order, sboxes,
-                     nv);
-  hipLaunchKernelGGL(nms_mask_kernel, dim3(words, words, n_img), dim3(64), 0, s, sboxes, nv, n_cand, words, thr, mask);
-  hipLaunchKernelGGL(nms_sweep_kernel, dim3(n_img), dim3(256), (size_t)64 * words * 8 + (size_t)max_keep * 4, s, mask,
-                     order, nv, n_cand, words, max_keep, keep, n_keep);
+  hipLaunchKernelGGL(nms_sort_kernel, dim3(n_img), dim3(NMS_T), 0, s, boxes, scores, valid, lvl, n_cand, b.order,
+                     b.sboxes, b.nv);
+  hipLaunchKernelGGL(nms_mask_kernel, dim3(words, words, n_img), dim3(64), 0, s, b.sboxes, b.nv, n_cand, words, thr,
+                     b.mask);
+  hipLaunchKernelGGL(nms_sweep_kernel, dim3(n_img), dim3(256), (size_t)64 * words * 8 + (size_t)max_keep * 4, s, b.mask,
+                     b.order, b.nv, n_cand, words, max_keep, keep, n_keep);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-static size_t sort_temp_bytes(size_t n) {
+bool nms_dims_ok(int n_cand) { return n_cand <= NMS_SORT_MAX && (n_cand + 63) / 64 <= 128; }
+
+size_t sort_temp_bytes(size_t n) {
   size_t bytes = 0;
   (void)rocprim::radix_sort_pairs(nullptr, bytes, (const unsigned long long*)nullptr, (unsigned long long*)nullptr,
                                   (const int32_t*)nullptr, (int32_t*)nullptr, n, 0u, 44u);
   return bytes;
 }
 
-size_t rpn_workspace_bytes(int n_img, int rows_per_img, int cand_total, int n_levels) {
-  const size_t n = (size_t)n_img * rows_per_img * 3;
-  const size_t sort_tmp = sort_temp_bytes(n);
-  (void)n_levels;
-  const size_t nc = (size_t)n_img * cand_total;
-  return n * 32 + ((sort_tmp + 255) & ~(size_t)255) + (size_t)n_img * 6 * 2 * 4 + nc * 24 + 18 * 256 +
-         nms_workspace_bytes(n_img, cand_total) + 4096;
+struct RpnBufs {
+  float* sc;
+  int32_t *ids, *ids_sorted;
+  unsigned long long *keys, *keys_sorted;
+  float *cboxes, *cscores;
+  uint8_t* cvalid;
+  int8_t* clvl;
+  NmsBufs nms;
+  char* sort_ws;
+  size_t sort_tmp;
+  int32_t* keep;
+};
+
+RpnBufs rpn_layout(Carver& c, int n_img, int rows_per_img, int K, int max_keep) {
+  const size_t n = (size_t)n_img * rows_per_img * 3, nk = (size_t)n_img * K;
+  RpnBufs b;
+  b.sc = c.take<float>(n);
+  b.ids = c.take<int32_t>(n);
+  b.ids_sorted = c.take<int32_t>(n);
+  b.keys = c.take<unsigned long long>(n);
+  b.keys_sorted = c.take<unsigned long long>(n);
+  b.cboxes = c.take<float>(nk * 4);
+  b.cscores = c.take<float>(nk);
+  b.cvalid = c.take<uint8_t>(nk);
+  b.clvl = c.take<int8_t>(nk);
+  b.nms = nms_layout(c, n_img, K);
+  b.sort_tmp = sort_temp_bytes(n);
+  b.sort_ws = c.take<char>(b.sort_tmp);
+  b.keep = c.take<int32_t>((size_t)n_img * max_keep);
+  return b;
+}
+
+struct RcnnBufs {
+  float *boxes, *scores;
+  uint8_t* valid;
+  NmsBufs nms;
+  int32_t* keep;
+};
+
+RcnnBufs rcnn_layout(Carver& c, int n_img, int max_rois, int max_det) {
+  const size_t nr = (size_t)n_img * max_rois;
+  RcnnBufs b;
+  b.boxes = c.take<float>(nr * 4);
+  b.scores = c.take<float>(nr);
+  b.valid = c.take<uint8_t>(nr);
+  b.nms = nms_layout(c, n_img, max_rois);
+  b.keep = c.take<int32_t>((size_t)n_img * max_det);
+  return b;
+}
+
+}  // namespace
+
+size_t nms_workspace_bytes(int n_img, int n_cand) { return measure(nms_layout, n_img, n_cand); }
+
+int nms_batched(const float* boxes, const float* scores, const uint8_t* valid, const int8_t* lvl, int n_img,
+                int n_cand, float thr, int max_keep, void* ws, size_t ws_bytes, int32_t* keep, int32_t* n_keep,
+                hipStream_t s) {
+  if (!nms_dims_ok(n_cand)) return -2;
+  Carver c(ws, ws_bytes);
+  const NmsBufs b = nms_layout(c, n_img, n_cand);
+  if (!c.fits()) return -5;
+  return nms_launch(boxes, scores, valid, lvl, n_img, n_cand, thr, max_keep, b, keep, n_keep, s);
+}
+
+size_t rpn_workspace_bytes(int n_img, int rows_per_img, int cand_total, int max_keep) {
+  return measure(rpn_layout, n_img, rows_per_img, cand_total, max_keep);
 }
 
 int rpn_proposals(const float* head, const DetLevels& lv, int n_img, int rows_per_img, float img_h, float img_w,
                   float iou_thr, int max_keep, void* ws, size_t ws_bytes, float* props, float* prop_scores,
-                  int32_t* n_props, int32_t* keep_buf, hipStream_t s) {
+                  int32_t* n_props, hipStream_t s) {
   const size_t n = (size_t)n_img * rows_per_img * 3;
   const int K = lv.cand_total;
-  char* p = static_cast<char*>(ws);
-  auto take = [&](size_t b) {
-    char* q = p;
-    p += (b + 255) & ~(size_t)255;
-    return q;
-  };
-  float* sc = reinterpret_cast<float*>(take(n * 4));
-  int32_t* ids = reinterpret_cast<int32_t*>(take(n * 4));
-  int32_t* ids_sorted = reinterpret_cast<int32_t*>(take(n * 4));
-  unsigned long long* keys = reinterpret_cast<unsigned long long*>(take(n * 8));
-  unsigned long long* keys_sorted = reinterpret_cast<unsigned long long*>(take(n * 8));
-  float* cboxes = reinterpret_cast<float*>(take((size_t)n_img * K * 16));
-  float* cscores = reinterpret_cast<float*>(take((size_t)n_img * K * 4));
-  uint8_t* cvalid = reinterpret_cast<uint8_t*>(take((size_t)n_img * K));
-  int8_t* clvl = reinterpret_cast<int8_t*>(take((size_t)n_img * K));
-  void* nms_ws = take(nms_workspace_bytes(n_img, K));
-  size_t sort_tmp = sort_temp_bytes(n);
-  void* sort_ws = take(sort_tmp);
-  if ((size_t)(p - static_cast<char*>(ws)) > ws_bytes) return -5;
-  hipLaunchKernelGGL(rpn_scores_kernel, blocks_for((int64_t)n), dim3(256), 0, s, head, lv, rows_per_img, n_img, sc, ids,
-                     keys);
-  if (rocprim::radix_sort_pairs(sort_ws, sort_tmp, keys, keys_sorted, ids, ids_sorted, n, 0u, 44u, s) != hipSuccess)
+  if (!nms_dims_ok(K)) return -2;
+  Carver c(ws, ws_bytes);
+  const RpnBufs b = rpn_layout(c, n_img, rows_per_img, K, max_keep);
+  if (!c.fits()) return -5;
+  hipLaunchKernelGGL(rpn_scores_kernel, blocks_for((int64_t)n), dim3(256), 0, s, head, lv, rows_per_img, n_img, b.sc,
+                     b.ids, b.keys);
+  size_t sort_tmp = b.sort_tmp;
+  if (rocprim::radix_sort_pairs(b.sort_ws, sort_tmp, b.keys, b.keys_sorted, b.ids, b.ids_sorted, n, 0u, 44u, s) !=
+      hipSuccess)
     return -1;
-  hipLaunchKernelGGL(rpn_decode_kernel, blocks_for((int64_t)n_img * K), dim3(256), 0, s, head, sc, ids_sorted,
-                     lv, n_img, rows_per_img, img_h, img_w, cboxes, cscores, cvalid, clvl);
-  int rc = nms_batched(cboxes, cscores, cvalid, clvl, n_img, K, iou_thr, max_keep, nms_ws, keep_buf, n_props, s);
+  hipLaunchKernelGGL(rpn_decode_kernel, blocks_for((int64_t)n_img * K), dim3(256), 0, s, head, b.sc, b.ids_sorted,
+                     lv, n_img, rows_per_img, img_h, img_w, b.cboxes, b.cscores, b.cvalid, b.clvl);
+  int rc = nms_launch(b.cboxes, b.cscores, b.cvalid, b.clvl, n_img, K, iou_thr, max_keep, b.nms, b.keep, n_props, s);
   if (rc) return rc;
-  hipLaunchKernelGGL(gather_boxes_kernel, blocks_for((int64_t)n_img * max_keep), dim3(256), 0, s, cboxes, cscores,
-                     keep_buf, n_img, K, max_keep, props, prop_scores);
+  hipLaunchKernelGGL(gather_boxes_kernel, blocks_for((int64_t)n_img * max_keep), dim3(256), 0, s, b.cboxes, b.cscores,
+                     b.keep, n_img, K, max_keep, props, prop_scores);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -882,29 +937,23 @@ int roi_align(const DetFeats& fs, const float* rois, const int32_t* n_rois, int 
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-size_t rcnn_workspace_bytes(int n_img, int max_rois) {
-  return (size_t)n_img * max_rois * 24 + nms_workspace_bytes(n_img, max_rois) + (size_t)n_img * 128 * 4 + 2048;
+size_t rcnn_workspace_bytes(int n_img, int max_rois, int max_det) {
+  return measure(rcnn_layout, n_img, max_rois, max_det);
 }
 
 int rcnn_post(const float* rois, const float* head, const int32_t* n_rois, int n_img, int max_rois, float img_h,
               float img_w, float inv_sw, float inv_sh, float score_thr, float iou_thr, int max_det, void* ws,
-              float* det_boxes, float* det_scores, int32_t* n_det, int32_t* keep_buf, hipStream_t s) {
-  char* p = static_cast<char*>(ws);
-  auto take = [&](size_t b) {
-    char* q = p;
-    p += (b + 255) & ~(size_t)255;
-    return q;
-  };
-  float* boxes = reinterpret_cast<float*>(take((size_t)n_img * max_rois * 16));
-  float* scores = reinterpret_cast<float*>(take((size_t)n_img * max_rois * 4));
-  uint8_t* valid = reinterpret_cast<uint8_t*>(take((size_t)n_img * max_rois));
-  void* nms_ws = take(nms_workspace_bytes(n_img, max_rois));
+              size_t ws_bytes, float* det_boxes, float* det_scores, int32_t* n_det, hipStream_t s) {
+  if (!nms_dims_ok(max_rois)) return -2;
+  Carver c(ws, ws_bytes);
+  const RcnnBufs b = rcnn_layout(c, n_img, max_rois, max_det);
+  if (!c.fits()) return -5;
   hipLaunchKernelGGL(rcnn_decode_kernel, blocks_for((int64_t)n_img * max_rois), dim3(256), 0, s, rois, head, n_rois,
-                     n_img, max_rois, img_h, img_w, inv_sw, inv_sh, score_thr, boxes, scores, valid);
-  int rc = nms_batched(boxes, scores, valid, nullptr, n_img, max_rois, iou_thr, max_det, nms_ws, keep_buf, n_det, s);
+                     n_img, max_rois, img_h, img_w, inv_sw, inv_sh, score_thr, b.boxes, b.scores, b.valid);
+  int rc = nms_launch(b.boxes, b.scores, b.valid, nullptr, n_img, max_rois, iou_thr, max_det, b.nms, b.keep, n_det, s);
   if (rc) return rc;
-  hipLaunchKernelGGL(gather_boxes_kernel, blocks_for((int64_t)n_img * max_det), dim3(256), 0, s, boxes, scores,
-                     keep_buf, n_img, max_rois, max_det, det_boxes, det_scores);
+  hipLaunchKernelGGL(gather_boxes_kernel, blocks_for((int64_t)n_img * max_det), dim3(256), 0, s, b.boxes, b.scores,
+                     b.keep, n_img, max_rois, max_det, det_boxes, det_scores);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

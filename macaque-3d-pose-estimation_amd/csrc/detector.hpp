@@ -52,19 +52,23 @@ int merge_gather(const float* x, int n_img, int H, int W, int C, float* out, hip
 int upsample_add(float* lo, const float* hi, int n_img, int Hl, int Wl, int Hh, int Wh, int C, hipStream_t s);
 int im2col3x3(const float* x, int n_img, int H, int W, int C, bf16_t* out, hipStream_t s);
 int subsample2(const float* x, int n_img, int H, int W, int C, float* out, hipStream_t s);
+// Workspaces: each *_workspace_bytes runs the stage's layout function (workspace.hpp) on a measuring carver, and the
+// launcher carves the same layout from (ws, ws_bytes), returning -5 before any launch if it does not fit.  The RPN's
+// and the RCNN's layouts hold the NMS's and the kept-index buffer.
 size_t nms_workspace_bytes(int n_img, int n_cand);
 int nms_batched(const float* boxes, const float* scores, const uint8_t* valid, const int8_t* lvl, int n_img,
-                int n_cand, float thr, int max_keep, void* ws, int32_t* keep, int32_t* n_keep, hipStream_t s);
-size_t rpn_workspace_bytes(int n_img, int rows_per_img, int cand_total, int n_levels);
+                int n_cand, float thr, int max_keep, void* ws, size_t ws_bytes, int32_t* keep, int32_t* n_keep,
+                hipStream_t s);
+size_t rpn_workspace_bytes(int n_img, int rows_per_img, int cand_total, int max_keep);
 int rpn_proposals(const float* head, const DetLevels& lv, int n_img, int rows_per_img, float img_h, float img_w,
                   float iou_thr, int max_keep, void* ws, size_t ws_bytes, float* props, float* prop_scores,
-                  int32_t* n_props, int32_t* keep_buf, hipStream_t s);
+                  int32_t* n_props, hipStream_t s);
 int roi_align(const DetFeats& fs, const float* rois, const int32_t* n_rois, int n_img, int max_rois, bf16_t* out,
               hipStream_t s);
-size_t rcnn_workspace_bytes(int n_img, int max_rois);
+size_t rcnn_workspace_bytes(int n_img, int max_rois, int max_det);
 int rcnn_post(const float* rois, const float* head, const int32_t* n_rois, int n_img, int max_rois, float img_h,
               float img_w, float inv_sw, float inv_sh, float score_thr, float iou_thr, int max_det, void* ws,
-              float* det_boxes, float* det_scores, int32_t* n_det, int32_t* keep_buf, hipStream_t s);
+              size_t ws_bytes, float* det_boxes, float* det_scores, int32_t* n_det, hipStream_t s);
 int det_topk_boxes(const float* dboxes, const float* dscores, const int32_t* dcount, int n_img, int max_det, int k,
                    float thr, double min_margin, double max_margin, double desired_ar, float* boxes, float* tight,
                    int32_t* img_of, int32_t* valid, hipStream_t s);

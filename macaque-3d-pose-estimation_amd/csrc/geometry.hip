@@ -5,6 +5,7 @@
 #include "geometry.hpp"
 #include "dlt_dev.hpp"
 #include "viterbi_dev.hpp"
+#include "workspace.hpp"
 
 namespace mq {
 
@@ -484,9 +485,30 @@ int triangulate_pinv(const double* cams, int C, const double* und, const uint8_t
 }
 
 
+namespace {
+
+struct AffinityBufs {
+  double *rays, *dist;  // [B][M][J][6] back-projected rays, [B][M][M] pair distances
+};
+
+AffinityBufs affinity_layout(Carver& c, int B, int M, int J) {
+  AffinityBufs b;
+  b.rays = c.take<double>((size_t)B * M * J * 6);
+  b.dist = c.take<double>((size_t)B * M * M);
+  return b;
+}
+
+}  // namespace
+
+size_t affinity_workspace_bytes(int B, int M, int J) { return measure(affinity_layout, B, M, J); }
+
 int geometry_affinity(const double* cams, int C, const double* pts, const int32_t* cam_of_det, int B, int M, int J,
-                      double thr_kp, double* rays, double* dist, double* out, hipStream_t s) {
+                      double thr_kp, void* ws, size_t ws_bytes, double* out, hipStream_t s) {
   if (B <= 0 || M <= 0) return 0;
+  Carver c(ws, ws_bytes);
+  const AffinityBufs b = affinity_layout(c, B, M, J);
+  if (!c.fits()) return -5;
+  double *rays = b.rays, *dist = b.dist;
   const int bmj = B * M * J;
   if (bmj > 0)
     hipLaunchKernelGGL(affinity_rays_kernel, dim3((bmj + 255) / 256), dim3(256), 0, s, cams, C, pts, cam_of_det,
@@ -498,25 +520,34 @@ int geometry_affinity(const double* cams, int C, const double* pts, const int32_
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-size_t viterbi_scratch_bytes(int A, int F, int C, int J, int n_back) {
-  const size_t chains = (size_t)A * C * J;
-  const size_t rows = chains * F;
-  return rows * n_back * (n_back + 4) * sizeof(double) + rows + rows * n_back + 512;
+namespace {
+
+// transitions, particle records (8-byte aligned), then the int8 particle counts and back-pointers, unpadded
+VitBufs viterbi_layout(Carver& c, int A, int F, int C, int J, int n_back) {
+  const size_t rows = (size_t)A * C * J * F, nb = n_back;
+  VitBufs W;
+  W.trans = c.take<double>(rows * nb * nb, 8);
+  W.part = c.take<double>(rows * nb * 4, 8);
+  W.cnt = c.take<int8_t>(rows, 1);
+  W.bk = c.take<int8_t>(rows * nb, 1);
+  return W;
 }
 
-// scratch: viterbi_scratch_bytes() -- transitions, particle records, particle counts, back-pointers.
+}  // namespace
+
+size_t viterbi_scratch_bytes(int A, int F, int C, int J, int n_back) {
+  return measure(viterbi_layout, A, F, C, J, n_back);
+}
+
 int viterbi_filter(const double* kp, int A, int F, int C, int J, double score_thr, int n_back, double thres_dist,
-                   void* scratch, double* out, hipStream_t s) {
+                   void* scratch, size_t scratch_bytes, double* out, hipStream_t s) {
   const int chains = A * C * J;
   if (chains <= 0 || F <= 0) return 0;
   if (n_back > 3 || n_back < 1) return -2;
   const size_t rows = (size_t)chains * F;
-  char* w = static_cast<char*>(scratch);
-  VitBufs W;
-  W.trans = reinterpret_cast<double*>(w);
-  W.part = reinterpret_cast<double*>(w + rows * n_back * n_back * sizeof(double));
-  W.cnt = reinterpret_cast<int8_t*>(w + rows * n_back * (n_back + 4) * sizeof(double));
-  W.bk = W.cnt + rows;
+  Carver c(scratch, scratch_bytes);
+  const VitBufs W = viterbi_layout(c, A, F, C, J, n_back);
+  if (!c.fits()) return -5;
   VitChain V{kp, F, C, J, n_back, score_thr};
   const size_t work = rows * n_back * n_back;
   hipLaunchKernelGGL(viterbi_trans_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, s, V, chains, thres_dist,

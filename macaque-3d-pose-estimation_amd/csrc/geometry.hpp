@@ -12,13 +12,14 @@ int reprojection_error(const double* cams, int C, const double* p3d, const doubl
 int triangulate_pinv(const double* cams, int C, const double* und, const uint8_t* use, int N, double* out,
                      hipStream_t s);
 int geometry_affinity(const double* cams, int C, const double* pts, const int32_t* cam_of_det, int B, int M, int J,
-                      double thr_kp, double* rays, double* dist, double* out, hipStream_t s);
+                      double thr_kp, void* ws, size_t ws_bytes, double* out, hipStream_t s);
+size_t affinity_workspace_bytes(int B, int M, int J);
 int viterbi_filter(const double* kp, int A, int F, int C, int J, double score_thr, int n_back, double thres_dist,
-                   void* scratch, double* out, hipStream_t s);
+                   void* scratch, size_t scratch_bytes, double* out, hipStream_t s);
 size_t viterbi_scratch_bytes(int A, int F, int C, int J, int n_back);
 int match_svt(const double* S, const int32_t* n_det, const int32_t* cam_of_det, int B, int Nmax, double alpha,
-              double lambda, double mu, double tol, int max_iter, int pselect, void* ws, uint8_t* match,
-              double* x_out, int32_t* iters, hipStream_t s);
+              double lambda, double mu, double tol, int max_iter, int pselect, void* ws, size_t ws_bytes,
+              uint8_t* match, double* x_out, int32_t* iters, hipStream_t s);
 size_t match_svt_workspace_bytes(int B, int Nmax);
 // step-3 tracklet lift (tracklet.hip)
 int tracklet_traces(const double* cams, int C, const int32_t* row_start, const int32_t* row_tid,

@@ -25,6 +25,7 @@
 // ceil(RI * 6 * JPEG_BLOCK_MAX_BITS / 8) bytes before stuffing and twice that after: the slot.  Every write to a
 // slot and to `out` is also guarded by the slot's and the caller's stride.
 #include "jpeg.hpp"
+#include "workspace.hpp"
 
 #include <string.h>
 
@@ -371,13 +372,27 @@ size_t jpeg_max_bytes(int H, int W, int ri) {
   return JPEG_HEADER_BYTES + (size_t)jpeg_n_intervals(H, W, ri) * (jpeg_slot_bytes(ri) + 2);
 }
 
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+namespace {
 
-size_t jpeg_workspace_bytes(int n, int H, int W, int ri) {
+struct JpegBufs {
+  int16_t* coef;      // [n][n_mcu][6 blocks][64]
+  uint8_t* scratch;   // [n][n_int] entropy-coded slots
+  int32_t *lens, *offs;
+};
+
+JpegBufs jpeg_layout(Carver& c, int n, int H, int W, int ri) {
   const size_t n_int = (size_t)n * jpeg_n_intervals(H, W, ri);
-  return align256((size_t)n * jpeg_n_mcu(H, W) * 768) + align256(n_int * jpeg_slot_bytes(ri)) +
-         2 * align256(n_int * sizeof(int32_t));
+  JpegBufs b;
+  b.coef = c.take<int16_t>((size_t)n * jpeg_n_mcu(H, W) * 384);
+  b.scratch = c.take<uint8_t>(n_int * jpeg_slot_bytes(ri));
+  b.lens = c.take<int32_t>(n_int);
+  b.offs = c.take<int32_t>(n_int);
+  return b;
 }
+
+}  // namespace
+
+size_t jpeg_workspace_bytes(int n, int H, int W, int ri) { return measure(jpeg_layout, n, H, W, ri); }
 
 int jpeg_make_header(int H, int W, int quality, int ri, JpegHeader& hdr, JpegQuant& q) {
   if (quality < 1 || quality > 100) return -2;
@@ -435,18 +450,17 @@ int jpeg_make_header(int H, int W, int quality, int ri, JpegHeader& hdr, JpegQua
 }
 
 int jpeg_encode(const uint8_t* frames, int64_t frame_stride, int n, int H, int W, int ri, const JpegHeader& hdr,
-                const JpegQuant& q, uint8_t* out, int64_t out_stride, int32_t* out_size, void* ws, hipStream_t s) {
+                const JpegQuant& q, uint8_t* out, int64_t out_stride, int32_t* out_size, void* ws, size_t ws_bytes,
+                hipStream_t s) {
   const int mcus_x = (W + 15) / 16;
   const int n_mcu = (int)jpeg_n_mcu(H, W), n_int = (int)jpeg_n_intervals(H, W, ri);
   const int slot = (int)jpeg_slot_bytes(ri);
-  uint8_t* w = static_cast<uint8_t*>(ws);
-  int16_t* coef = reinterpret_cast<int16_t*>(w);
-  w += align256((size_t)n * n_mcu * 768);
-  uint8_t* scratch = w;
-  w += align256((size_t)n * n_int * slot);
-  int32_t* lens = reinterpret_cast<int32_t*>(w);
-  w += align256((size_t)n * n_int * sizeof(int32_t));
-  int32_t* offs = reinterpret_cast<int32_t*>(w);
+  Carver c(ws, ws_bytes);
+  const JpegBufs b = jpeg_layout(c, n, H, W, ri);
+  if (!c.fits()) return -5;
+  int16_t* coef = b.coef;
+  uint8_t* scratch = b.scratch;
+  int32_t *lens = b.lens, *offs = b.offs;
 
   const dim3 g_dct((n_mcu + DCT_MCUS - 1) / DCT_MCUS, n);
   // 16-byte loads when every row of every frame starts on a 16-byte boundary and holds whole MCUs

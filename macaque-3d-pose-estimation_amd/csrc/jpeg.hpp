@@ -27,8 +27,9 @@ size_t jpeg_max_bytes(int H, int W, int ri);
 size_t jpeg_workspace_bytes(int n, int H, int W, int ri);
 // 0, or -2 on a quality outside [1, 100]
 int jpeg_make_header(int H, int W, int quality, int ri, JpegHeader& hdr, JpegQuant& q);
-// the three stages on stream s; ws holds jpeg_workspace_bytes
+// the three stages on stream s; -5 if the ws_bytes at ws are fewer than jpeg_workspace_bytes
 int jpeg_encode(const uint8_t* frames, int64_t frame_stride, int n, int H, int W, int ri, const JpegHeader& hdr,
-                const JpegQuant& q, uint8_t* out, int64_t out_stride, int32_t* out_size, void* ws, hipStream_t s);
+                const JpegQuant& q, uint8_t* out, int64_t out_stride, int32_t* out_size, void* ws, size_t ws_bytes,
+                hipStream_t s);
 
 }  // namespace mq

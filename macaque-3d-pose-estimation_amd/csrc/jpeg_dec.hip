@@ -23,6 +23,7 @@
 // <= 63 within a block).  Planes are MCU-padded, so the IDCT stores whole blocks; the colour kernel reads chroma
 // inside the true extent and writes pixels x < W, y < H of its own frame only.
 #include "jpeg_dec.hpp"
+#include "workspace.hpp"
 
 #include <limits.h>
 #include <string.h>
@@ -257,8 +258,6 @@ __global__ __launch_bounds__(COL_THREADS) void jpeg_colour_kernel(const uint8_t*
 }
 
 // -------------------------------------------------------------------------------------------------- host
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 int jpeg_dec_geom(const mq_jpeg_info& info, JpegDecGeom& g) {
   if (info.height < 1 || info.height > 65535 || info.width < 1 || info.width > 65535) return -2;
   if (info.n_comp != 1 && info.n_comp != 3) return -2;
@@ -289,29 +288,42 @@ int jpeg_dec_geom(const mq_jpeg_info& info, JpegDecGeom& g) {
   return 0;
 }
 
-size_t jpeg_dec_workspace_bytes(int n, const JpegDecGeom& g) {
-  return align256((size_t)n * g.n_mcu * g.n_blocks * 128) + align256((size_t)n * g.y_bytes) +
-         2 * align256((size_t)n * g.c_bytes) + align256((size_t)n * g.n_int * sizeof(int32_t)) +
-         align256((size_t)n * sizeof(int32_t));
+namespace {
+
+struct JpegDecBufs {
+  int16_t* coef;  // [n][n_mcu][n_blocks][64]
+  size_t n_coef;
+  uint8_t *plane_y, *plane_cb, *plane_cr;
+  int32_t *iv_end, *frame_ok;
+};
+
+JpegDecBufs jpeg_dec_layout(Carver& c, int n, const JpegDecGeom& g) {
+  JpegDecBufs b;
+  b.n_coef = (size_t)n * g.n_mcu * g.n_blocks * 64;
+  b.coef = c.take<int16_t>(b.n_coef);
+  b.plane_y = c.take<uint8_t>((size_t)n * g.y_bytes);
+  b.plane_cb = c.take<uint8_t>((size_t)n * g.c_bytes);
+  b.plane_cr = c.take<uint8_t>((size_t)n * g.c_bytes);
+  b.iv_end = c.take<int32_t>((size_t)n * g.n_int);
+  b.frame_ok = c.take<int32_t>(n);
+  return b;
 }
 
-int jpeg_decode(const uint8_t* streams, int64_t stream_stride, const int32_t* sizes, int n, const mq_jpeg_info& info,
-                const JpegDecGeom& g, uint8_t* frames, int64_t frame_stride, int32_t* status, void* ws, hipStream_t s) {
-  uint8_t* w = static_cast<uint8_t*>(ws);
-  int16_t* coef = reinterpret_cast<int16_t*>(w);
-  const size_t coef_bytes = (size_t)n * g.n_mcu * g.n_blocks * 128;
-  w += align256(coef_bytes);
-  uint8_t* plane_y = w;
-  w += align256((size_t)n * g.y_bytes);
-  uint8_t* plane_cb = w;
-  w += align256((size_t)n * g.c_bytes);
-  uint8_t* plane_cr = w;
-  w += align256((size_t)n * g.c_bytes);
-  int32_t* iv_end = reinterpret_cast<int32_t*>(w);
-  w += align256((size_t)n * g.n_int * sizeof(int32_t));
-  int32_t* frame_ok = reinterpret_cast<int32_t*>(w);
+}  // namespace
 
-  if (hipMemsetAsync(coef, 0, coef_bytes, s) != hipSuccess) return -1;
+size_t jpeg_dec_workspace_bytes(int n, const JpegDecGeom& g) { return measure(jpeg_dec_layout, n, g); }
+
+int jpeg_decode(const uint8_t* streams, int64_t stream_stride, const int32_t* sizes, int n, const mq_jpeg_info& info,
+                const JpegDecGeom& g, uint8_t* frames, int64_t frame_stride, int32_t* status, void* ws, size_t ws_bytes,
+                hipStream_t s) {
+  Carver c(ws, ws_bytes);
+  const JpegDecBufs b = jpeg_dec_layout(c, n, g);
+  if (!c.fits()) return -5;
+  int16_t* coef = b.coef;
+  uint8_t *plane_y = b.plane_y, *plane_cb = b.plane_cb, *plane_cr = b.plane_cr;
+  int32_t *iv_end = b.iv_end, *frame_ok = b.frame_ok;
+
+  if (hipMemsetAsync(coef, 0, b.n_coef * sizeof(int16_t), s) != hipSuccess) return -1;
   const int vec = (uintptr_t)streams % 16 == 0 && stream_stride % 16 == 0;
   hipLaunchKernelGGL(jpeg_dec_markers_kernel, dim3(n), dim3(MRK_THREADS), 0, s, streams, stream_stride, sizes,
                      (int64_t)info.scan_offset, g.n_int, vec, iv_end, frame_ok, status);

@@ -24,8 +24,9 @@ struct JpegDecGeom {
 // 0, or -2 for an info that mq_jpeg_parse could not have filled
 int jpeg_dec_geom(const mq_jpeg_info& info, JpegDecGeom& g);
 size_t jpeg_dec_workspace_bytes(int n, const JpegDecGeom& g);
-// the memset and the four kernels on stream s; ws holds jpeg_dec_workspace_bytes
+// the memset and the four kernels on stream s; -5 if the ws_bytes at ws are fewer than jpeg_dec_workspace_bytes
 int jpeg_decode(const uint8_t* streams, int64_t stream_stride, const int32_t* sizes, int n, const mq_jpeg_info& info,
-                const JpegDecGeom& g, uint8_t* frames, int64_t frame_stride, int32_t* status, void* ws, hipStream_t s);
+                const JpegDecGeom& g, uint8_t* frames, int64_t frame_stride, int32_t* status, void* ws, size_t ws_bytes,
+                hipStream_t s);
 
 }  // namespace mq

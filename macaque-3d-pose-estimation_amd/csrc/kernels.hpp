@@ -114,21 +114,21 @@ size_t optim_workspace_bytes(int B, int F, int J, int NL);
 int optim_points(const double* cams, int C, const double* p2d, double* x, int B, int F, int J, const int* cons_host,
                  int n_strong, int n_weak, const double* ssf_host, double scale_length, double scale_length_weak,
                  double rp, int loss, int n_deriv, int fix_lengths, int max_iter, double ftol, void* ws,
-                 double* stats, hipStream_t s);
+                 size_t ws_bytes, double* stats, hipStream_t s);
 // the scipy-faithful trust-region solver (optim_trf.hip); stats (B, 8)
 extern int g_optim_trf_chunk;
 extern int g_optim_trf_fb;
-size_t optim_trf_workspace_bytes(int B, int F, int J, int C, int NL);
+size_t optim_trf_workspace_bytes(int B, int F, int J, int C, int NL, int n_deriv);
 int optim_points_trf(const double* cams, int C, const double* p2d, double* x, int B, int F, int J, const int* cons_host,
                      int n_strong, int n_weak, const double* ssf_host, double scale_length, double scale_length_weak,
                      double rp, int loss, int n_deriv, int fix_lengths, int max_nfev, double ftol, void* ws,
-                     double* stats, hipStream_t s);
+                     size_t ws_bytes, double* stats, hipStream_t s);
 
 // csrc/optim_possible.hip: optim_points_possible (the trf algorithm on the soft choice among candidate 2D peaks)
-size_t optim_possible_workspace_bytes(int B, int F, int J, int C, int P, int NL);
+size_t optim_possible_workspace_bytes(int B, int F, int J, int C, int P, int NL, int n_deriv);
 int optim_points_possible(const double* cams, int C, const double* p2d, double* x, double* anorm, int B, int F, int J,
                           int P, const int* cons_host, int n_strong, int n_weak, const double* ssf_host,
                           double scale_length, double scale_length_weak, double rp, int loss, int n_deriv,
-                          int max_nfev, double ftol, void* ws, double* stats, hipStream_t s);
+                          int max_nfev, double ftol, void* ws, size_t ws_bytes, double* stats, hipStream_t s);
 
 }  // namespace mq

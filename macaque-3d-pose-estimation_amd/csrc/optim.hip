@@ -27,6 +27,7 @@
 #include "camera.hpp"
 #include "common.hpp"
 #include "optim_dev.hpp"
+#include "workspace.hpp"
 
 namespace mq {
 namespace {
@@ -1504,29 +1505,63 @@ int g_optim_stop = 6;        // stop rule bits: 1 model-agreement ratio > 0.25 (
                              // ftol alone stopped up to 1.5 % above scipy's cost on one; ftol / 2 at or below it on all,
                              // profiles/r04r_optim_parity_probe_seeds.log)
 
-size_t optim_workspace_bytes(int B, int F, int J, int NL) {
-  const size_t NV = (size_t)F * J * 3 + NL;
-  size_t n = 0;
-  n += (size_t)B * NV * 9;                       // g diag d r z P0 P1 q xt
-  n += (size_t)B * F * J * 6;                    // R
-  n += (size_t)B * F * NL * 5;                   // lenJ
-  n += (size_t)B * F * 2;                        // costF pqF
-  n += (size_t)B * F * NL;                       // qLf
-  n += (size_t)B * J * F * OPT_FS + (size_t)B * OPT_MAXL;  // fac pinvL
-  n += (size_t)B * J * F * 18 * OPT_MAXN + 2;               // mn (+ 16-B alignment)
-  n += (size_t)B * (OPT_MAXIT + 1) * (J + 2);    // rzJ, pq
-  n += (size_t)B * 5;                            // cost, cost_t + pred (2), ctl(2)
-  n += (size_t)NL + 2 + B;                       // constraint pairs (int32), ssf
-  return n * sizeof(double);
+namespace {
+
+// The LM driver's workspace, carved in doubles (align 8).  Bf's input pointers (cams, p2d) are the caller's.
+struct OptWork {
+  OptBufs Bf;
+  double *xt, *cost_t, *ctl, *ssf;
+  int* cons;
+};
+
+OptWork optim_layout(Carver& c, int B, int F, int J, int NL) {
+  const size_t NVB = (size_t)B * ((size_t)F * J * 3 + NL);
+  auto take = [&](size_t cnt) { return c.take<double>(cnt, 8); };
+  OptWork W{};
+  OptBufs& Bf = W.Bf;
+  Bf.g = take(NVB);
+  Bf.diag = take(NVB);
+  Bf.d = take(NVB);
+  Bf.r = take(NVB);
+  Bf.z = take(NVB);
+  Bf.P0 = take(NVB);
+  Bf.P1 = take(NVB);
+  Bf.q = take(NVB);
+  W.xt = take(NVB);
+  Bf.R = take((size_t)B * F * J * 6);
+  Bf.lenJ = take((size_t)B * F * NL * 5);
+  Bf.costF = take((size_t)B * F);
+  Bf.pqF = take((size_t)B * F);
+  Bf.qLf = take((size_t)B * F * NL);
+  Bf.fac = take((size_t)B * J * F * OPT_FS);
+  Bf.mn = take((size_t)B * J * F * 18 * OPT_MAXN + 2);
+  if (reinterpret_cast<uintptr_t>(Bf.mn) & 15) ++Bf.mn;  // 16-B aligned for the LDS-DMA (the base is 256-B aligned)
+  Bf.pinvL = take((size_t)B * OPT_MAXL);
+  Bf.rzJ = take((size_t)B * (OPT_MAXIT + 1) * (J + 1));
+  Bf.pq = take((size_t)B * (OPT_MAXIT + 1));
+  Bf.cost = take(B);
+  W.cost_t = take(2 * (size_t)B);  // trial costs, then the predicted reductions (one copy back)
+  W.ctl = take(2 * (size_t)B);
+  Bf.ctl = W.ctl;
+  // small host-side inputs go to the device through the workspace tail; the int pairs are rounded to doubles
+  W.cons = reinterpret_cast<int*>(take((NL * 2 + 1) / 2 + 1));
+  W.ssf = take(B);
+  Bf.cons = W.cons;
+  Bf.ssf = W.ssf;
+  return W;
 }
 
-// Host driver.  x: device (B, NV) in/out.  cons/ssf/stats: host.  ws: device workspace of
-// optim_workspace_bytes().  stats[b*4 + {0,1,2,3}] = initial cost, final cost, LM iterations, status
-// (1 ftol, 2 max_iter, 3 damping overflow).
+}  // namespace
+
+size_t optim_workspace_bytes(int B, int F, int J, int NL) { return measure(optim_layout, B, F, J, NL); }
+
+// Host driver.  x: device (B, NV) in/out.  cons/ssf/stats: host.  ws: device workspace of at least
+// optim_workspace_bytes() (-5 if ws_bytes is fewer).  stats[b*4 + {0,1,2,3}] = initial cost, final cost, LM
+// iterations, status (1 ftol, 2 max_iter, 3 damping overflow).
 int optim_points(const double* cams, int C, const double* p2d, double* x, int B, int F, int J, const int* cons_host,
                  int n_strong, int n_weak, const double* ssf_host, double scale_length, double scale_length_weak,
                  double rp, int loss, int n_deriv, int fix_lengths, int max_iter, double ftol, void* ws,
-                 double* stats, hipStream_t s) {
+                 size_t ws_bytes, double* stats, hipStream_t s) {
   const int NL = n_strong + n_weak;
   if (B <= 0 || F <= 0 || J <= 0) return 0;
   if (J > OPT_MAXJ || NL > OPT_MAXL || C > OPT_MAXC || C < 1 || n_deriv < 1 || n_deriv > OPT_MAXN) return -2;
@@ -1554,45 +1589,14 @@ int optim_points(const double* cams, int C, const double* p2d, double* x, int B,
     }
   }
   const size_t NVB = (size_t)B * D.NV;
-  double* w = static_cast<double*>(ws);
-  OptBufs Bf{};
-  auto take = [&](size_t cnt) {
-    double* p = w;
-    w += cnt;
-    return p;
-  };
-  Bf.g = take(NVB);
-  Bf.diag = take(NVB);
-  Bf.d = take(NVB);
-  Bf.r = take(NVB);
-  Bf.z = take(NVB);
-  Bf.P0 = take(NVB);
-  Bf.P1 = take(NVB);
-  Bf.q = take(NVB);
-  double* xt = take(NVB);
-  Bf.R = take((size_t)B * F * J * 6);
-  Bf.lenJ = take((size_t)B * F * NL * 5);
-  Bf.costF = take((size_t)B * F);
-  Bf.pqF = take((size_t)B * F);
-  Bf.qLf = take((size_t)B * F * NL);
-  Bf.fac = take((size_t)B * J * F * OPT_FS);
-  Bf.mn = take((size_t)B * J * F * 18 * OPT_MAXN + 2);
-  if (reinterpret_cast<uintptr_t>(Bf.mn) & 15) ++Bf.mn;  // 16-B aligned for the LDS-DMA
-  Bf.pinvL = take((size_t)B * OPT_MAXL);
-  Bf.rzJ = take((size_t)B * (OPT_MAXIT + 1) * (J + 1));
-  Bf.pq = take((size_t)B * (OPT_MAXIT + 1));
-  Bf.cost = take(B);
-  double* cost_t = take(2 * (size_t)B);   // trial costs, then the predicted reductions (one copy back)
-  double* pred_d = cost_t + B;
-  double* ctl = take(2 * (size_t)B);
-  Bf.ctl = ctl;
+  Carver carver(ws, ws_bytes);
+  const OptWork W = optim_layout(carver, B, F, J, NL);
+  if (!carver.fits()) return -5;
+  OptBufs Bf = W.Bf;
   Bf.cams = cams;
   Bf.p2d = p2d;
-  // small host-side inputs go to the device through the workspace tail
-  int* cons_d = reinterpret_cast<int*>(take((NL * 2 + 1) / 2 + 1));
-  double* ssf_d = take(B);
-  Bf.cons = cons_d;
-  Bf.ssf = ssf_d;
+  double *xt = W.xt, *cost_t = W.cost_t, *pred_d = cost_t + B, *ctl = W.ctl, *ssf_d = W.ssf;
+  int* cons_d = W.cons;
   if (hipMemcpyAsync(cons_d, cons_host, sizeof(int) * 2 * NL, hipMemcpyHostToDevice, s) != hipSuccess) return -3;
   if (hipMemcpyAsync(ssf_d, ssf_host, sizeof(double) * B, hipMemcpyHostToDevice, s) != hipSuccess) return -3;
 

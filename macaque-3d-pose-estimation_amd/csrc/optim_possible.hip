@@ -42,6 +42,7 @@
 #include "common.hpp"
 #include "optim_dev.hpp"
 #include "trf_host.hpp"
+#include "workspace.hpp"
 
 extern "C" int mq_trust_region_2d(const double* B, const double* g, double Delta, double* p);
 
@@ -947,14 +948,60 @@ int poss_frames_per_block(int J, int C, int P, int NL) {
 
 }  // namespace
 
-size_t optim_possible_workspace_bytes(int B, int F, int J, int C, int P, int NL) {
+namespace {
+
+// The driver's workspace, carved in doubles (align 8; the int arrays are rounded to doubles).  Bf's input pointers
+// (cams, p2d) are the caller's; the host-written inputs also as the pointers the driver uploads through.
+struct PossWork {
+  PossBufs Bf;
+  double *ctl, *ssf;
+  int *act, *done, *cons;
+};
+
+PossWork poss_layout(Carver& c, int B, int F, int J, int C, int P, int NL, int n_deriv) {
   const size_t NC = (size_t)C * F * J, NV = (size_t)F * J * 3 + NL + NC * P;
-  const size_t M = 3 * NC + (size_t)F * J * 3 + (size_t)NL * F;
-  const size_t NB = ((size_t)F + poss_frames_per_block(J, C, P, NL) - 1) / poss_frames_per_block(J, C, P, NL);
-  size_t n = (size_t)B * (10 * NV + 4 * M + NC * 6 + NC * 3 * P + (size_t)F * NL * 4);
-  n += (size_t)B * NB * (POSS_NPF + 6 + NL) + 2 * (size_t)B * POSS_NS;
-  n += (size_t)B * 8 + NL + 8;
-  return n * sizeof(double) + 256;
+  const size_t M = 3 * NC + (size_t)(F - n_deriv) * J * 3 + (size_t)NL * F;
+  const size_t FB = poss_frames_per_block(J, C, P, NL), BNB = (size_t)B * (((size_t)F + FB - 1) / FB);
+  const size_t NVB = (size_t)B * NV, MB = (size_t)B * M;
+  auto take = [&](size_t cnt) { return c.take<double>(cnt, 8); };
+  PossWork W{};
+  PossBufs& Bf = W.Bf;
+  Bf.x = take(NVB);
+  Bf.xt = take(NVB);
+  Bf.g = take(NVB);
+  Bf.vraw = take(NVB);
+  Bf.vn = take(NVB);
+  Bf.h = take(NVB);
+  Bf.hbar = take(NVB);
+  Bf.xl = take(NVB);
+  Bf.s1 = take(NVB);
+  Bf.s2 = take(NVB);
+  Bf.f = take(MB);
+  Bf.u = take(MB);
+  Bf.js1 = take(MB);
+  Bf.js2 = take(MB);
+  Bf.Jx = take((size_t)B * NC * 6);
+  Bf.Ja = take((size_t)B * NC * 3 * P);
+  Bf.lenJ = take((size_t)B * F * NL * 4);
+  Bf.part = take(BNB * POSS_NPF);
+  Bf.upart = take(2 * BNB);
+  Bf.vpart = take(2 * BNB);
+  Bf.xpart = take(2 * BNB);
+  Bf.Lpart = take(BNB * NL);
+  Bf.st = take(2 * (size_t)B * POSS_NS);
+  Bf.itn = take(B);
+  Bf.ctl = W.ctl = take(4 * (size_t)B);
+  Bf.ssf = W.ssf = take(B);
+  Bf.act = W.act = reinterpret_cast<int*>(take(((size_t)B + 1) / 2 + 1));
+  Bf.done = W.done = reinterpret_cast<int*>(take(((size_t)B + 1) / 2 + 1));
+  Bf.cons = W.cons = reinterpret_cast<int*>(take((size_t)NL + 1));
+  return W;
+}
+
+}  // namespace
+
+size_t optim_possible_workspace_bytes(int B, int F, int J, int C, int P, int NL, int n_deriv) {
+  return measure(poss_layout, B, F, J, C, P, NL, n_deriv);
 }
 
 // Host driver: the trf_no_bounds loop (scipy 1.15.3 optimize/_lsq/trf.py:401-540; oracle/trf.py), every animal on
@@ -963,7 +1010,8 @@ size_t optim_possible_workspace_bytes(int B, int F, int J, int C, int P, int NL)
 int optim_points_possible(const double* cams, int C, const double* p2d, double* x, double* anorm, int B, int F, int J,
                           int P, const int* cons_host, int n_strong, int n_weak, const double* ssf_host,
                           double scale_length, double scale_length_weak, double rp, int loss, int n_deriv,
-                          int max_nfev_arg, double ftol, void* ws, double* stats, hipStream_t s) {
+                          int max_nfev_arg, double ftol, void* ws, size_t ws_bytes, double* stats,
+                          hipStream_t s) {
   const int NL = n_strong + n_weak;
   if (B <= 0 || F <= 0 || J <= 0) return 0;
   if (P < 1 || P > POSS_MAXP || n_deriv < 1 || n_deriv > 3 || F <= n_deriv || C < 1 || NL > POSS_MAXL) return -2;
@@ -1005,50 +1053,15 @@ int optim_points_possible(const double* cams, int C, const double* p2d, double* 
   const size_t lds = poss_lds_bytes(D.FB, n_deriv, J, C, P, NL);
   if (lds > POSS_LDS_MAX) return -2;
   const int NB = D.NB;
-  const size_t NVB = (size_t)B * D.NV, MB = (size_t)B * D.M, BNB = (size_t)B * NB;
-  double* w = static_cast<double*>(ws);
-  auto take = [&](size_t cnt) {
-    double* p = w;
-    w += cnt;
-    return p;
-  };
-  PossBufs Bf{};
-  Bf.x = take(NVB);
-  Bf.xt = take(NVB);
-  Bf.g = take(NVB);
-  Bf.vraw = take(NVB);
-  Bf.vn = take(NVB);
-  Bf.h = take(NVB);
-  Bf.hbar = take(NVB);
-  Bf.xl = take(NVB);
-  Bf.s1 = take(NVB);
-  Bf.s2 = take(NVB);
-  Bf.f = take(MB);
-  Bf.u = take(MB);
-  Bf.js1 = take(MB);
-  Bf.js2 = take(MB);
-  Bf.Jx = take((size_t)B * D.NC * 6);
-  Bf.Ja = take((size_t)B * D.NC * 3 * P);
-  Bf.lenJ = take((size_t)B * F * NL * 4);
-  Bf.part = take(BNB * POSS_NPF);
-  Bf.upart = take(2 * BNB);
-  Bf.vpart = take(2 * BNB);
-  Bf.xpart = take(2 * BNB);
-  Bf.Lpart = take(BNB * NL);
-  Bf.st = take(2 * (size_t)B * POSS_NS);
-  Bf.itn = take(B);
-  double* ctl_d = take(4 * (size_t)B);
-  double* ssf_d = take(B);
-  int* act_d = reinterpret_cast<int*>(take(((size_t)B + 1) / 2 + 1));
-  int* done_d = reinterpret_cast<int*>(take(((size_t)B + 1) / 2 + 1));
-  int* cons_d = reinterpret_cast<int*>(take((size_t)NL + 1));
+  const size_t BNB = (size_t)B * NB;
+  Carver carver(ws, ws_bytes);
+  const PossWork W = poss_layout(carver, B, F, J, C, P, NL, n_deriv);
+  if (!carver.fits()) return -5;
+  PossBufs Bf = W.Bf;
   Bf.cams = cams;
   Bf.p2d = p2d;
-  Bf.cons = cons_d;
-  Bf.ssf = ssf_d;
-  Bf.act = act_d;
-  Bf.ctl = ctl_d;
-  Bf.done = done_d;
+  double *ctl_d = W.ctl, *ssf_d = W.ssf;
+  int *act_d = W.act, *done_d = W.done, *cons_d = W.cons;
 
   std::vector<int> act(B, 1), doneh(B, 0);
   std::vector<double> ctl(4 * (size_t)B, 0.0), part(BNB * POSS_NPF, 0.0), itnh(B, 0.0);

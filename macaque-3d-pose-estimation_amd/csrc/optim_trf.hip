@@ -42,6 +42,7 @@
 #include "lsmr_dev.hpp"
 #include "optim_dev.hpp"
 #include "trf_host.hpp"
+#include "workspace.hpp"
 
 namespace mq {
 namespace {
@@ -1105,8 +1106,7 @@ constexpr size_t TRF_DYN_LDS = 128 * 1024;  // (the kernels' static LDS stays un
 // the grid still has a CU per workgroup: the smallest count whose grid, for TRF_NOMINAL_B animals, fits the
 // nominal CUs (TRF_NOMINAL_CUS below), else `fit` (profiles/r05u_*: 24 frames x 4 animals 8 % faster at 1 frame than at 4; 300 x 4,
 // which fills the CUs at 4, 60 % slower at 1).  The choice depends on F, not on the batch, so an animal's
-// result does not depend on which animals share its call (the reductions follow the blocks).  Monotonic in
-// `fit`, so the workspace, sized at the deepest smoothing order, never has fewer blocks than a call.
+// result does not depend on which animals share its call (the reductions follow the blocks).
 constexpr int TRF_NOMINAL_B = 4;  // the reference's four individuals
 // The block decomposition (frames per workgroup, the length variables' own workgroup) is sized for a nominal
 // MI355X (256 CUs), not for the device at hand: the reductions follow the blocks, so an optim_points result
@@ -1128,21 +1128,66 @@ int trf_frames_per_block(int J, int C, int NL, int n, int F) {
   return fit;
 }
 
-size_t optim_trf_workspace_bytes(int B, int F, int J, int C, int NL) {
-  const size_t NV = (size_t)F * J * 3 + NL, MR = ((size_t)J * C * 2 + (size_t)J * 3 + NL + 1) & ~(size_t)1;
-  const int FB = trf_frames_per_block(J, C, NL, TRF_MAXN, F);
-  const size_t NB = ((size_t)F + FB - 1) / FB;
-  size_t n = 0;
-  n += (size_t)B * F * MR * 3;           // fres ftr u
-  n += (size_t)B * F * J * C * 6;        // Jrep
-  n += (size_t)B * F * NL * 4;           // lenJ
-  n += (size_t)B * NV * 10;              // g vraw vn h hbar xl s1 s2 xt (+1)
-  n += (size_t)B * NB * (NL + 2 + 2 + NL) + 4 * (size_t)B * (NB + 1);  // fL upart xpart Lpart vpart (the host-read
-                                                                         // partials are host-mapped)
-  n += 2 * (size_t)B * TRF_NS + (size_t)B * 8;
-  n += (size_t)NL + 2 + 2 * (size_t)B + 16;  // cons, act, done, ssf
-  n += ((size_t)J + 1 + 2 * (size_t)NL) / 2 + 1;  // jadj
-  return n * sizeof(double) + 256;
+namespace {
+
+// The trf driver's workspace, carved in doubles (align 8; the int arrays are rounded to doubles).  Bf's input
+// pointers (cams, p2d) and its host-mapped partials are the driver's.
+struct TrfWork {
+  TrfBufs Bf;
+  double *xt, *ssf;
+  int *cons, *jadj, *done, *act;
+  char* ctl_end;  // the end of the host-written inputs
+};
+
+TrfWork trf_layout(Carver& c, int B, int F, int J, int C, int NL, int n_deriv) {
+  const size_t MR = ((size_t)J * C * 2 + (size_t)J * 3 + NL + 1) & ~(size_t)1;
+  const size_t FB = trf_frames_per_block(J, C, NL, n_deriv, F), NB = ((size_t)F + FB - 1) / FB;
+  const size_t NVB = (size_t)B * ((size_t)F * J * 3 + NL), MB = (size_t)B * F * MR;
+  auto take = [&](size_t cnt) { return c.take<double>(cnt, 8); };
+  TrfWork W{};
+  TrfBufs& Bf = W.Bf;
+  Bf.fres = take(MB);
+  Bf.ftr = take(MB);
+  Bf.u = take(MB);
+  Bf.Jrep = take((size_t)B * F * J * C * 6);
+  Bf.lenJ = take((size_t)B * F * NL * 4);
+  Bf.g = take(NVB);
+  Bf.vraw = take(NVB);
+  Bf.vn = take(NVB);
+  Bf.h = take(NVB);
+  Bf.hbar = take(NVB);
+  Bf.xl = take(NVB);
+  Bf.s1 = take(NVB);
+  Bf.s2 = take(NVB);
+  W.xt = take(NVB);
+  Bf.fL = take((size_t)B * NB * NL);
+  Bf.upart = take(2 * (size_t)B * NB);
+  Bf.vpart = take(2 * (size_t)B * (NB + 1) * 2);
+  Bf.xpart = take(2 * (size_t)B * NB);
+  Bf.Lpart = take((size_t)B * NB * NL);
+  Bf.st = take(2 * (size_t)B * TRF_NS);
+  // the host-written inputs, one contiguous run in upload order, so that each group of them the driver sends
+  // together (call setup; lsmr setup: lctl, done, act; a trial: act, coef) is one copy
+  W.cons = reinterpret_cast<int*>(take(((size_t)NL * 2 + 1) / 2 + 1));
+  W.jadj = reinterpret_cast<int*>(take(((size_t)J + 1 + 2 * (size_t)NL) / 2 + 1));
+  W.ssf = take(B);
+  Bf.lctl = take(4 * (size_t)B);
+  W.done = reinterpret_cast<int*>(take(((size_t)B + 1) / 2 + 1));
+  W.act = reinterpret_cast<int*>(take(((size_t)B + 1) / 2 + 1));
+  Bf.coef = take(4 * (size_t)B);
+  W.ctl_end = c.take<char>(0, 1);
+  Bf.cons = W.cons;
+  Bf.jadj = W.jadj;
+  Bf.ssf = W.ssf;
+  Bf.act = W.act;
+  Bf.done = W.done;
+  return W;
+}
+
+}  // namespace
+
+size_t optim_trf_workspace_bytes(int B, int F, int J, int C, int NL, int n_deriv) {
+  return measure(trf_layout, B, F, J, C, NL, n_deriv);
 }
 
 // Host driver: the trf_no_bounds loop (trf.py:401-540) as mq::TrfAnimal's steps with this solver's launches in
@@ -1152,7 +1197,7 @@ size_t optim_trf_workspace_bytes(int B, int F, int J, int C, int NL) {
 int optim_points_trf(const double* cams, int C, const double* p2d, double* x, int B, int F, int J, const int* cons_host,
                      int n_strong, int n_weak, const double* ssf_host, double scale_length, double scale_length_weak,
                      double rp, int loss, int n_deriv, int fix_lengths, int max_nfev_arg, double ftol, void* ws,
-                     double* stats, hipStream_t s) {
+                     size_t ws_bytes, double* stats, hipStream_t s) {
   const int NL = n_strong + n_weak;
   if (B <= 0 || F <= 0 || J <= 0) return 0;
   if (J > TRF_MAXJ || NL > TRF_MAXL || C > 16 || C < 1 || n_deriv < 1 || n_deriv > TRF_MAXN) return -2;
@@ -1181,51 +1226,15 @@ int optim_points_trf(const double* cams, int C, const double* p2d, double* x, in
   D.ctol = 1.0 / 1e8;
   trf_diff_coefficients(n_deriv, D.c);
   const int NB = D.NB;
-  const size_t NVB = (size_t)B * D.NV, MB = (size_t)B * F * D.MR;
-  double* w = static_cast<double*>(ws);
-  auto take = [&](size_t cnt) {
-    double* p = w;
-    w += cnt;
-    return p;
-  };
-  TrfBufs Bf{};
-  Bf.fres = take(MB);
-  Bf.ftr = take(MB);
-  Bf.u = take(MB);
-  Bf.Jrep = take((size_t)B * F * J * C * 6);
-  Bf.lenJ = take((size_t)B * F * NL * 4);
-  Bf.g = take(NVB);
-  Bf.vraw = take(NVB);
-  Bf.vn = take(NVB);
-  Bf.h = take(NVB);
-  Bf.hbar = take(NVB);
-  Bf.xl = take(NVB);
-  Bf.s1 = take(NVB);
-  Bf.s2 = take(NVB);
-  double* xt = take(NVB);
-  Bf.fL = take((size_t)B * NB * NL);
-  Bf.upart = take(2 * (size_t)B * NB);
-  Bf.vpart = take(2 * (size_t)B * (NB + 1) * 2);
-  Bf.xpart = take(2 * (size_t)B * NB);
-  Bf.Lpart = take((size_t)B * NB * NL);
-  Bf.st = take(2 * (size_t)B * TRF_NS);
-  // the host-written inputs, one contiguous run in upload order, so that each group of them the driver sends
-  // together (call setup; lsmr setup: lctl, done, act; a trial: act, coef) is one copy
-  int* cons_d = reinterpret_cast<int*>(take(((size_t)NL * 2 + 1) / 2 + 1));
-  int* jadj_d = reinterpret_cast<int*>(take(((size_t)J + 1 + 2 * (size_t)NL) / 2 + 1));
-  double* ssf_d = take(B);
-  Bf.lctl = take(4 * (size_t)B);
-  int* done_d = reinterpret_cast<int*>(take(((size_t)B + 1) / 2 + 1));
-  int* act_d = reinterpret_cast<int*>(take(((size_t)B + 1) / 2 + 1));
-  Bf.coef = take(4 * (size_t)B);
-  char* const ctl_end = reinterpret_cast<char*>(w);
+  Carver carver(ws, ws_bytes);
+  const TrfWork W = trf_layout(carver, B, F, J, C, NL, n_deriv);
+  if (!carver.fits()) return -5;
+  TrfBufs Bf = W.Bf;
   Bf.cams = cams;
   Bf.p2d = p2d;
-  Bf.cons = cons_d;
-  Bf.jadj = jadj_d;
-  Bf.ssf = ssf_d;
-  Bf.act = act_d;
-  Bf.done = done_d;
+  double *xt = W.xt, *ssf_d = W.ssf;
+  int *cons_d = W.cons, *jadj_d = W.jadj, *done_d = W.done, *act_d = W.act;
+  char* const ctl_end = W.ctl_end;
   // Every small transfer of the driver goes through pinned memory: a copy from or to pageable memory waits for
   // the stream (tens of microseconds per copy, several per trust-region iteration).  Uploads are staged in an
   // arena that is recycled at each stream synchronisation (a copy still queued reads its own slot); downloads
